@@ -12,6 +12,10 @@ over RCCL (the path's only exchange).  Prints ONE JSON line on rank 0.
 `python bench.py --gpus N` starts its own N ranks (one process per GPU, spawned before anything
 touches a GPU) unless a launcher (torch.distributed.run) already set RANK / WORLD_SIZE.
 `--backend gloo --dry-run` runs the launcher and the gather on the CPU without a device (tests).
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds the legs that take runs
+of their own (CPU baseline and parity, the other precisions, the cfg3_strong job); `--dump-outputs DIR`
+writes what the last timed step returned as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -76,7 +80,17 @@ def parse(argv=None):
                    help="torch.distributed backend of the gather (nccl = RCCL on ROCm)")
     p.add_argument("--dry-run", action="store_true",
                    help="no device: launcher, rendezvous and the gather only (CPU tests of the N > 1 plumbing)")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline and the parity block "
+                        "(--cpu-seconds), the other precisions (--variants) and the cfg3_strong job (--cfg3-strong); "
+                        "without --full those three are off whatever their options say")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                        "(float64; rank 0): U, the applied moves of every QP of the job, and for cfg2 x, the solver's "
+                        "solutions; an array above 24 MiB is cut to a fixed, seeded sample of its rows")
     a = p.parse_args(argv)
+    if not a.full:
+        a.variants, a.cfg3_strong, a.cpu_seconds = 0, 0, 0.0
     if a.dtype is None:  # the fastest path inside north_star's 1e-5 on the applied move
         a.dtype = {"cfg2": "mixed", "perplant": "f64", "stream": "f64"}.get(a.workload, "f32")
     if a.workload == "stream" and a.batch == 65536:
@@ -259,6 +273,8 @@ def main_quadrotor(a, rank, world, local, dist, dev):
     kern_ms = float(np.mean([s.elapsed_time(e) for s, e in ev]))
     setup_ms = float(np.mean([s.elapsed_time(m_) for (s, _), m_ in zip(ev, ev_mid)]))
     solve_ms = float(np.mean([m_.elapsed_time(e) for (_, e), m_ in zip(ev, ev_mid)]))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a, {"U": _job_moves(a, got, B * world, world)})
     status, iters, rho = solver.info()
     n = N * nu
     # factorisations: the initial inverse plus (at least) one per QP whose rho moved
@@ -365,6 +381,32 @@ def _timed_loop(a, step, dist, world, dev):
     return wall, got
 
 
+DUMP_MAX_BYTES = 24 << 20  # per array; a run dumps at most two (under 64 MB in all)
+
+
+def _job_moves(a, got, total, world):
+    """Rank 0's gathered moves of the last step as one host array: U of the job's QPs in global order."""
+    import torch
+
+    from solvempc_amd import dist as mdist
+
+    full = mdist.unpad(got, total, world) if a.scaling == "strong" else torch.cat(list(got))
+    return full.cpu().numpy().copy()
+
+
+def dump_outputs(a, arrays: dict) -> None:
+    """--dump-outputs: DIR/<name>.npy in float64.  An array above DUMP_MAX_BYTES keeps a fixed sample of its rows
+    (sorted draws of a generator seeded with 0: the same rows in every run of the same arguments)."""
+    out = Path(a.dump_outputs)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, v in arrays.items():
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.nbytes > DUMP_MAX_BYTES:
+            keep = max(1, DUMP_MAX_BYTES // (v.nbytes // len(v)))
+            v = v[np.sort(np.random.default_rng(0).choice(len(v), size=keep, replace=False))]
+        np.save(out / f"{name}.npy", v)
+
+
 def traffic_per_solve(name, batch, N):
     """HBM bytes of one bench step of the dominant kernel from the committed PMC pass of the same bench
     command (tools/gpu.sh pmc:<workload>,<dtype> -> tools/pmc_traffic.py -> profiles/pmc_traffic_<name>.json),
@@ -423,6 +465,8 @@ def main_dry(a, rank, world, dist):
     rec["dry_run"] = True
     rec["collective"] = _collective(dist, world, got)
     full = (mdist.unpad(got, total, world) if a.scaling == "strong" else torch.cat(got)).numpy()
+    if a.dump_outputs:
+        dump_outputs(a, {"U": full})
     rec["collective"]["gathered"] = int(full.size)
     rec["collective"]["matches_stream"] = bool(np.array_equal(full, workload.mpc_states(a.seed, 0, total)[1]))
     return rec
@@ -571,6 +615,13 @@ def main_lti(a, rank, world, local, dist, dev):
         U_d = pg.finish()  # the last step's moves
     kern_ms = float(np.mean([s.elapsed_time(e) for s, e in ev]))
     U_out = U_d[:B].cpu().numpy().copy()  # this step's applied U (the parity block's device side)
+    if a.dump_outputs and rank == 0:  # (before the variants below reuse U_d)
+        arrays = {"U": _job_moves(a, got, total, world)}
+        if stream_mode:
+            arrays["X"] = X_d.cpu().numpy()  # rank 0's plant states after the last control step
+        elif not perplant:
+            arrays["x"] = solver.solution()  # rank 0's QP solutions (batch, n)
+        dump_outputs(a, arrays)
 
     status, iters, rho_f = solver.info()
     # cfg2 at N = 1: the other precisions on the same batch with the same protocol (the `variants` block)

@@ -123,7 +123,7 @@ def test_bench_launches_its_own_ranks():
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--dry-run",
-                        "--steps", "3", "--warmup", "1", "--batch", "1000", "--cfg3-global-batch", "1001"],
+                        "--full", "--steps", "3", "--warmup", "1", "--batch", "1000", "--cfg3-global-batch", "1001"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

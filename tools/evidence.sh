@@ -11,7 +11,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-me
 tail -1 "$out/tests.log"
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 || { echo "smoke failed"; exit 1; }
 for wl in cfg2 perplant quadrotor stream; do
-  timeout -k 10 600 python -u bench.py --workload $wl > "$out/bench_$wl.json" 2> "$out/bench_$wl.err" \
+  timeout -k 10 600 python -u bench.py --full --workload $wl > "$out/bench_$wl.json" 2> "$out/bench_$wl.err" \
     || { echo "bench $wl failed"; tail -20 "$out/bench_$wl.err"; exit 1; }
   echo "bench $wl ok"
 done

@@ -24,8 +24,8 @@ for step in "$@"; do
     smoke)
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 \
         || { echo "smoke failed"; tail -20 "$out/smoke.log"; exit 1; } ;;
-    bench)  # bench:<args with _ for spaces>, e.g. bench:--workload_quadrotor
-      timeout -k 10 600 python -u bench.py ${arg//_/ } > "$out/bench_$arg.json" 2> "$out/bench_$arg.err" \
+    bench)  # bench:<args with _ for spaces>, e.g. bench:--workload_quadrotor (the whole line: bench.py --full)
+      timeout -k 10 600 python -u bench.py --full ${arg//_/ } > "$out/bench_$arg.json" 2> "$out/bench_$arg.err" \
         || { echo "bench failed"; tail -20 "$out/bench_$arg.err"; exit 1; } ;;
     probe)
       timeout -k 10 600 python -u tools/order_probe.py $arg > "$out/probe_$arg.log" 2>&1 \
