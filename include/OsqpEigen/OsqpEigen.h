@@ -45,7 +45,7 @@ namespace OsqpEigen {
 class Settings {
 public:
     Settings() { mpcq_default_settings(&s_); }
-    void resetDefaultSettings() { mpcq_default_settings(&s_); polish_ = false; }
+    void resetDefaultSettings() { mpcq_default_settings(&s_); }
     void setRho(double v) { s_.rho = v; }
     void setSigma(double v) { s_.sigma = v; }
     void setScaling(int v) { s_.scaling = v; }
@@ -60,20 +60,18 @@ public:
     void setDualInfeasibilityTollerance(double v) { s_.eps_dual_inf = v; }
     void setAlpha(double v) { s_.alpha = v; }
     void setLinearSystemSolver(int) {}  // the device factorisation replaces QDLDL / MKL Pardiso
-    void setDelta(double) {}            // polishing only
-    void setPolish(bool v) { polish_ = v; }  // not implemented: initSolver() fails when set
-    void setPolishRefineIter(int) {}
+    void setDelta(double v) { s_.delta = v; }  // solution polishing on the device (mpcq_settings)
+    void setPolish(bool v) { s_.polish = v; }
+    void setPolishRefineIter(int v) { s_.polish_refine_iter = v; }
     void setVerbosity(bool v) { s_.verbose = v; }
     void setScaledTerimination(bool v) { s_.scaled_termination = v; }
     void setCheckTermination(int v) { s_.check_termination = v; }
     void setWarmStart(bool v) { s_.warm_start = v; }
     void setTimeLimit(double) {}  // OSQP's time limit is a PROFILING feature; unsupported, ignored
     const mpcq_settings &getSettings() const { return s_; }
-    bool polish() const { return polish_; }
 
 private:
     mpcq_settings s_;
-    bool polish_ = false;
 };
 
 /* osqp-eigen Data: sizes first, then the problem arrays (copied at set time). */
@@ -150,7 +148,6 @@ public:
     bool initSolver()
     {
         if (ctx_) return fail("initSolver: the solver is already initialised");
-        if (settings_->polish()) return fail("initSolver: solution polishing is not supported");
         const Data &d = *data_;
         if (!d.isSet()) return fail("initSolver: the problem data are not set");
         mpcq_dims dims{d.n_, d.m_, 1, 1, MPCQ_F64, device_};
@@ -232,12 +229,15 @@ public:
         if (mpcq_get_info(ctx_, &status_, &iter_, &rho) != MPCQ_OK) return fail("solve");
         if (mpcq_get_solution(ctx_, x_.data()) != MPCQ_OK) return fail("solve");
         if (data_->m_ && mpcq_get_dual(ctx_, y_.data()) != MPCQ_OK) return fail("solve");
+        if (mpcq_get_polish_info(ctx_, &polish_status_, nullptr, nullptr, nullptr) != MPCQ_OK) return fail("solve");
         return status_ == MPCQ_SOLVED;
     }
     const Eigen::VectorXd &getSolution() const { return x_; }
     const Eigen::VectorXd &getDualSolution() const { return y_; }
     int getStatus() const { return status_; }
     int getIterations() const { return iter_; }
+    /* OSQP info->status_polish of the last solve: 1 successful, -1 unsuccessful, 0 not performed */
+    int getPolishStatus() const { return polish_status_; }
     const std::string &lastError() const { return err_; }
 
 private:
@@ -253,7 +253,7 @@ private:
     int device_;
     mpcq_ctx *ctx_ = nullptr;
     Eigen::VectorXd x_, y_, l_, u_;  // solution; current bounds (the update calls' u >= l check)
-    int status_ = MPCQ_UNSOLVED, iter_ = 0;
+    int status_ = MPCQ_UNSOLVED, iter_ = 0, polish_status_ = 0;
     std::string err_;
 };
 

@@ -65,13 +65,25 @@ extern "C" {
 
 /* OSQP v0.6 settings (osqp constants.h defaults via mpcq_default_settings).  Replaces
  * OsqpEigen::Settings as used at ModelPredictiveControlAPI.cpp:51-52 (setVerbosity,
- * setWarmStart(true)); polish is not supported (the reference leaves it off). */
+ * setWarmStart(true)).
+ * polish (off by default, as the reference leaves it): OSQP's solution polishing (polish.c) of every QP
+ * that ended MPCQ_SOLVED, run on the device after the ADMM in fp64 whatever the context's dtype: the
+ * active set is guessed from the final iterate, the delta-regularised reduced KKT system is solved with
+ * polish_refine_iter steps of iterative refinement, and the polished (x, y) replaces the ADMM's where it
+ * reduces the residuals (mpcq_get_polish_info).  mpcq_solve, mpcq_mpc_step_device and mpcq_mpc_step honour
+ * it; the contexts it serves have n <= 32 and m <= 64 (mpcq_create refuses larger ones with polish set),
+ * and the single-launch entry points (mpcq_mpc_run_device, mpcq_mpc_plants_step_device, mpcq_mimo_*), which
+ * cannot fit a second pass, return MPCQ_ERR_ARG on a context whose polish is set.  With polish == 0 every
+ * code path, launch and result is what it is without the setting. */
 typedef struct mpcq_settings {
     double rho, sigma, alpha;
     double eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
     double adaptive_rho_tolerance, adaptive_rho_fraction;
     int max_iter, check_termination, scaling, adaptive_rho, adaptive_rho_interval;
     int warm_start, scaled_termination, verbose;
+    int polish;             /* 0 (default) / 1                                                */
+    int polish_refine_iter; /* iterative refinement steps of the polish solve (default 3)    */
+    double delta;           /* regularisation of the polish KKT system (default 1e-6)        */
 } mpcq_settings;
 
 typedef struct mpcq_dims {
@@ -145,6 +157,13 @@ int mpcq_get_solution(mpcq_ctx *ctx, double *x);            /* batch*n */
 int mpcq_get_dual(mpcq_ctx *ctx, double *y);                /* batch*m */
 int mpcq_get_info(mpcq_ctx *ctx, int *status, int *iter, double *rho); /* each batch, may be NULL */
 int mpcq_get_scaling(mpcq_ctx *ctx, double *D, double *E, double *c); /* plant 0: n, m, 1 */
+/* Polish outcome of the last solve (OSQP info->status_polish and the polished residuals; synchronises).
+ * Each argument is a host array of `batch` entries and may be NULL.  status_polish: 1 successful,
+ * -1 unsuccessful (the ADMM solution was kept), 0 not performed (settings.polish == 0, or the QP did not
+ * end MPCQ_SOLVED); n_active: rows of the reduced KKT system (lower-active + upper-active); pri_res,
+ * dua_res: residuals of the returned solution in the termination norm (unscaled unless
+ * scaled_termination), NaN where status_polish == 0. */
+int mpcq_get_polish_info(mpcq_ctx *ctx, int *status_polish, int *n_active, double *pri_res, double *dua_res);
 
 /* Device path the next solve takes (no OSQP counterpart; for benchmarks and tests):
  * *kind = MPCQ_PATH_TILE (shared plant, MFMA tile kernel's phase chain), MPCQ_PATH_WAVE

@@ -146,6 +146,18 @@ class BatchSolver:
                                         it.ctypes.data_as(C.POINTER(C.c_int)), _dp(rho)), "mpcq_get_info")
         return st, it, rho
 
+    def polish_info(self):
+        """(status_polish, n_active, pri_res, dua_res) of the last solve (mpcq_get_polish_info): OSQP's
+        status_polish per QP (1 successful, -1 unsuccessful, 0 not performed), the rows of its reduced KKT
+        system, and the returned solution's residuals (NaN where polish was not performed)."""
+        sp = np.empty(self.batch, dtype=np.int32)
+        na = np.empty(self.batch, dtype=np.int32)
+        pri, dua = np.empty(self.batch), np.empty(self.batch)
+        ip = C.POINTER(C.c_int)
+        _capi.check(lib().mpcq_get_polish_info(self._ctx, sp.ctypes.data_as(ip), na.ctypes.data_as(ip), _dp(pri),
+                                               _dp(dua)), "mpcq_get_polish_info")
+        return sp, na, pri, dua
+
     def scaling(self):
         D, E, c = np.empty(self.n), np.empty(self.m), C.c_double()
         _capi.check(lib().mpcq_get_scaling(self._ctx, _dp(D), _dp(E), C.byref(c)), "mpcq_get_scaling")

@@ -21,7 +21,7 @@ EXPORTS = (
     "mpcq_mpc_step", "mpcq_mpc_set_plant", "mpcq_mpc_simulate_device", "mpcq_mpc_run_device",
     "mpcq_condense", "mpcq_mpc_setup_plants_device", "mpcq_last_error", "mpcq_get_path",
     "mpcq_mimo_setup_plants_device", "mpcq_mimo_step_device", "mpcq_mpc_stream_counters",
-    "mpcq_mpc_plants_step_device", "mpcq_get_stream_path", "mpcq_get_order",
+    "mpcq_mpc_plants_step_device", "mpcq_get_stream_path", "mpcq_get_order", "mpcq_get_polish_info",
 )
 
 
@@ -40,6 +40,7 @@ class Settings(C.Structure):
         ("max_iter", C.c_int), ("check_termination", C.c_int), ("scaling", C.c_int),
         ("adaptive_rho", C.c_int), ("adaptive_rho_interval", C.c_int),
         ("warm_start", C.c_int), ("scaled_termination", C.c_int), ("verbose", C.c_int),
+        ("polish", C.c_int), ("polish_refine_iter", C.c_int), ("delta", C.c_double),
     ]
 
 
@@ -87,6 +88,7 @@ def lib() -> C.CDLL:
         "mpcq_get_dual": (C.c_int, [vp, dp]),
         "mpcq_get_info": (C.c_int, [vp, ip, ip, dp]),
         "mpcq_get_scaling": (C.c_int, [vp, dp, dp, dp]),
+        "mpcq_get_polish_info": (C.c_int, [vp, ip, ip, dp, dp]),
         "mpcq_mimo_setup_plants_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 9 + [vp]),
         "mpcq_mimo_step_device": (C.c_int, [vp, vp, vp, vp, vp]),
         "mpcq_get_path": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

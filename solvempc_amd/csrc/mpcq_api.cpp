@@ -172,6 +172,12 @@ struct mpcq_ctx {
     // into d_status, d_iter before anything reads those (get_info, the device view, verbose, the publish
     // kernel of materialize_xy)
     bool info_lazy = false;
+    // settings.polish (mpcq_polish.hip): status_polish and the reduced system's rows per QP, the returned
+    // solution's (primal, dual) residual pairs; allocated only when polish is set.  pol_valid: the last solve
+    // filled them (mpcq_get_polish_info reports "not performed" otherwise)
+    int *d_pol_status = nullptr, *d_pol_nact = nullptr;
+    double *d_pol_res = nullptr;
+    bool pol_valid = false;
     // host copies of plant-0 scaling
     std::vector<double> hD, hE;
     double hc = 1.0;
@@ -317,6 +323,13 @@ bool lower_all_free_batch(const mpcq_ctx *c, const double *l)
     return true;
 }
 
+// The single-launch entry points cannot fit the polish pass (include/mpcq.h mpcq_settings)
+std::string polish_refusal(const char *fn)
+{
+    return std::string(fn) + ": settings.polish is set, and this single-launch path has no polish pass (use mpcq_solve / "
+                             "mpcq_mpc_step_device / mpcq_mpc_step, or a context without polish)";
+}
+
 enum Need { kNone, kGeneric, kAnySetup };
 
 // kGeneric: the generic / condensed-MPC operators (the generic kernels run on them); kAnySetup:
@@ -402,6 +415,9 @@ void mpcq_default_settings(mpcq_settings *s)
     s->warm_start = 1;
     s->scaled_termination = 0;
     s->verbose = 0;
+    s->polish = 0;
+    s->polish_refine_iter = 3;
+    s->delta = 1e-6;
 }
 
 const char *mpcq_last_error(void) { return g_err.c_str(); }
@@ -418,8 +434,11 @@ int mpcq_create(const mpcq_dims *d, const mpcq_settings *s, mpcq_ctx **out)
     if (s) st = *s;
     if (st.rho <= 0 || st.sigma <= 0 || st.alpha <= 0 || st.alpha >= 2 || st.max_iter <= 0 ||
         st.eps_abs < 0 || st.eps_rel < 0 || (st.eps_abs == 0 && st.eps_rel == 0) || st.scaling < 0 ||
-        st.check_termination < 0 || st.adaptive_rho_tolerance < 1 || st.adaptive_rho_interval < 0)
+        st.check_termination < 0 || st.adaptive_rho_tolerance < 1 || st.adaptive_rho_interval < 0 ||
+        !(st.delta > 0) || st.polish_refine_iter < 0)
         return fail(MPCQ_ERR_ARG, "invalid settings (osqp validate_settings)");
+    if (st.polish && (d->n > 32 || d->m > 64))
+        return fail(MPCQ_ERR_ARG, "settings.polish serves n <= 32, m <= 64 (the polish kernel's capacities)");
     int nc = 0, mc = 0;
     const int KN = (d->n + 3) / 4, KM = (std::max(d->m, 1) + 3) / 4;
     const bool tile = d->n_plants == 1 && mpcq_internal_tile_supported(KN, KM) &&
@@ -495,6 +514,11 @@ int mpcq_create(const mpcq_dims *d, const mpcq_settings *s, mpcq_ctx **out)
         A(&c->d_snx, es * B * nc);
         A(&c->d_sny, es * B * mc);
     }
+    if (st.polish) {
+        A((void **)&c->d_pol_status, 4 * B);
+        A((void **)&c->d_pol_nact, 4 * B);
+        A((void **)&c->d_pol_res, 8 * 2 * B);
+    }
     if (!ok) {
         mpcq_destroy(c);
         return fail(MPCQ_ERR_HIP, "hipMalloc failed");
@@ -514,7 +538,8 @@ int mpcq_destroy(mpcq_ctx *c)
                     c->d_xs, c->d_zs, c->d_ys, c->d_rhos, c->d_snx, c->d_sny, c->d_Fx, c->d_Fu, c->d_Fr,
                     c->d_Sbar, c->d_Ku, c->d_W0, c->d_X, c->d_U, c->d_img, c->d_list, c->d_counts,
                     c->d_itstate, c->d_Ad, c->d_Bd, c->d_step, c->d_flags, c->d_stamps, c->d_mimo,
-                    c->d_it_acc, c->d_uns_acc, c->d_Xs, c->d_Us, c->d_ordmap, c->d_ord};
+                    c->d_it_acc, c->d_uns_acc, c->d_Xs, c->d_Us, c->d_ordmap, c->d_ord, c->d_pol_status,
+                    c->d_pol_nact, c->d_pol_res};
     if (c->gexec) (void)hipGraphExecDestroy(c->gexec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     for (void *p : ptrs)
@@ -987,6 +1012,7 @@ static int launch_typed(mpcq_ctx *c, hipStream_t s, bool mpc, const double *X, d
     auto a = make_args<T>(c);
     if (mpc) {
         a.mpc = 1; a.mpc_u = 1; a.nx = c->nx; a.X = X; a.U = U; a.xref = xref;
+        if (c->set.polish) a.mpc_u = 0;  // (the applied move is the polished one: polish_kernel's U += x[0])
         a.Fx = c->d_Fx; a.Fu = c->d_Fu; a.Fr = c->d_Fr; a.Sbar = c->d_Sbar; a.Ku = c->d_Ku; a.W0 = c->d_W0;
         const bool lazy = c->tile && choose_path(c).kind == MPCQ_PATH_TILE && c->d_Xs && c->d_Us;
         if (lazy) {  // phase 0 saves X, U (40 B/QP) instead of writing q, u (480 B/QP): materialize_qu
@@ -1045,7 +1071,8 @@ static void verbose_header(const mpcq_ctx *c, const char *what)
     else std::printf("          check_termination: off,\n");
     std::printf("          scaling: %s, scaled_termination: %s\n", s.scaling ? "on" : "off",
                 s.scaled_termination ? "on" : "off");
-    std::printf("          warm start: %s, polish: off, time_limit: off\n\n", s.warm_start ? "on" : "off");
+    std::printf("          warm start: %s, polish: %s, time_limit: off\n\n", s.warm_start ? "on" : "off",
+                s.polish ? "on" : "off");
     std::fflush(stdout);
 }
 
@@ -1091,7 +1118,13 @@ static void verbose_solve(mpcq_ctx *c, double seconds)
     std::printf("iter   objective    pri res    dua res    rho        time\n");
     if (have && sol) std::printf("%4d  %12.4e  %9.2e  %9.2e  %9.2e  %9.2es\n\n", it[0], obj, pri, dua, rho[0], seconds);
     else std::printf("%4d  %12s  %9s  %9s  %9.2e  %9.2es\n\n", it[0], "-", "-", "-", rho[0], seconds);
+    std::vector<int> pst;
+    if (c->set.polish && c->pol_valid) {
+        pst.resize(B);
+        if (hipMemcpy(pst.data(), c->d_pol_status, 4 * B, hipMemcpyDeviceToHost) != hipSuccess) pst.clear();
+    }
     std::printf("status:               %s\n", status_name(st[0]));
+    if (!pst.empty() && pst[0]) std::printf("solution polish:      %s\n", pst[0] == 1 ? "successful" : "unsuccessful");
     std::printf("number of iterations: %d\n", it[0]);
     if (have && sol) std::printf("optimal objective:    %.4f\n", obj);
     std::printf("run time:             %.2es\n", seconds);
@@ -1106,11 +1139,62 @@ static void verbose_solve(mpcq_ctx *c, double seconds)
             mn = std::min(mn, it[b]);
             mx = std::max(mx, it[b]);
         }
-        std::printf("batch:                %zu QPs, %zu solved, iterations %d / %.1f / %d (min / mean / max)\n", B,
-                    solved, mn, (double)tot / B, mx);
+        if (pst.empty()) {
+            std::printf("batch:                %zu QPs, %zu solved, iterations %d / %.1f / %d (min / mean / max)\n", B,
+                        solved, mn, (double)tot / B, mx);
+        } else {
+            size_t polished = 0;
+            for (size_t b = 0; b < B; b++) polished += pst[b] == 1;
+            std::printf("batch:                %zu QPs, %zu solved, %zu polished, iterations %d / %.1f / %d (min / mean / "
+                        "max)\n", B, solved, polished, mn, (double)tot / B, mx);
+        }
     }
     std::printf("\n");
     std::fflush(stdout);
+}
+
+// settings.polish: OSQP's polish of every SOLVED QP of the solve just enqueued on s (mpcq_polish.hip), one
+// more launch on the same stream.  Whatever the solve left lazy (q, u of a tile-path controllerStep; x, y,
+// rho, status, iter of a tile chain) is published first, on the same stream (c->last == s), so the kernel
+// reads this solve's data and results and every later reader finds d_x, d_y, d_status, d_iter complete.
+static int launch_polish(mpcq_ctx *c, hipStream_t s, double *U)
+{
+    int rc = materialize_qu(c);
+    if (rc || (rc = materialize_info(c)) || (rc = materialize_xy(c)) || (rc = materialize_rho(c))) return rc;
+    mpcq::PolishArgs a{};
+    a.batch = c->dims.batch;
+    a.n = c->dims.n;
+    a.m = c->dims.m;
+    a.nc = c->nc;
+    a.mc = c->mc;
+    a.shared = c->dims.n_plants == 1;
+    a.is_f32 = c->dims.dtype == MPCQ_F32;
+    a.ops_stride = c->ops_stride;
+    a.ops = c->d_ops;
+    a.P = c->d_P;
+    a.A = c->d_A;
+    a.q = c->d_q;
+    a.l = c->d_l;
+    a.u = c->d_u;
+    a.xs = c->d_xs;
+    a.zs = c->d_zs;
+    a.ys = c->d_ys;
+    a.status = c->d_status;
+    a.x = c->d_x;
+    a.y = c->d_y;
+    a.U = U;
+    a.pol_status = c->d_pol_status;
+    a.pol_nact = c->d_pol_nact;
+    a.pol_res = c->d_pol_res;
+    a.delta = c->set.delta;
+    a.refine = c->set.polish_refine_iter;
+    a.scaled_termination = c->set.scaled_termination;
+    hipError_t err = hipSuccess;
+    const int prc = mpcq_internal_polish_launch(&a, c->cus, s, &err);
+    if (prc == -1) return fail(MPCQ_ERR_ARG, "polish: the kernel serves n <= 32, m <= 64");
+    if (prc) return fail(MPCQ_ERR_HIP, std::string("polish kernel launch failed: ") + hipGetErrorString(err));
+    c->pol_valid = true;
+    return MPCQ_OK;
 }
 
 extern "C" {
@@ -1127,6 +1211,10 @@ static int launch_solve(mpcq_ctx *c, hipStream_t s, bool mpc, const double *X, d
     if (rc) return fail(MPCQ_ERR_HIP, std::string("ADMM kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
     c->last = s;
     c->fresh = false;
+    c->pol_valid = false;
+    if (c->set.polish) {
+        if (int prc = launch_polish(c, s, mpc ? U : nullptr)) return prc;
+    }
     // settings.verbose: the summary needs the results on the host, so it synchronises the stream, which a
     // stream under capture (mpcq_mpc_run_device's per-step graph) must not do: there the replay loop prints
     // after each replayed step instead
@@ -1199,6 +1287,34 @@ int mpcq_get_scaling(mpcq_ctx *c, double *D, double *E, double *cc)
     if (D) std::copy(c->hD.begin(), c->hD.end(), D);
     if (E) std::copy(c->hE.begin(), c->hE.end(), E);
     if (cc) *cc = c->hc;
+    return MPCQ_OK;
+}
+
+int mpcq_get_polish_info(mpcq_ctx *c, int *status_polish, int *n_active, double *pri_res, double *dua_res)
+{
+    int rc = check_ctx(c, kAnySetup);
+    if (rc) return rc;
+    const size_t B = c->dims.batch;
+    if (!c->set.polish || !c->pol_valid) {  // not performed
+        HIPCHK(hipStreamSynchronize(c->last));
+        for (size_t b = 0; b < B; b++) {
+            if (status_polish) status_polish[b] = 0;
+            if (n_active) n_active[b] = 0;
+            if (pri_res) pri_res[b] = std::nan("");
+            if (dua_res) dua_res[b] = std::nan("");
+        }
+        return MPCQ_OK;
+    }
+    if ((rc = d2h(c, status_polish, c->d_pol_status, 4 * B)) || (rc = d2h(c, n_active, c->d_pol_nact, 4 * B))) return rc;
+    if (pri_res || dua_res) {
+        std::vector<double> res(2 * B);
+        if ((rc = d2h(c, res.data(), c->d_pol_res, 8 * 2 * B))) return rc;
+        for (size_t b = 0; b < B; b++) {
+            if (pri_res) pri_res[b] = res[2 * b];
+            if (dua_res) dua_res[b] = res[2 * b + 1];
+        }
+    }
+    HIPCHK(hipStreamSynchronize(c->last));
     return MPCQ_OK;
 }
 
@@ -1620,6 +1736,7 @@ int mpcq_mpc_run_device(mpcq_ctx *c, double *X, double *U, double xref, int step
 {
     int rc = check_ctx(c, kGeneric);
     if (rc) return rc;
+    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal("mpcq_mpc_run_device"));
     if (!c->mpc_ready || !c->plant_nx) return fail(MPCQ_ERR_ORDER, "mpc operators / plant not set");
     if (c->plant_nx != c->nx) return fail(MPCQ_ERR_ARG, "plant nx differs from the operators' nx");
     if (!X || !U || steps < 0) return fail(MPCQ_ERR_ARG, "null X/U or steps < 0");
@@ -1883,6 +2000,7 @@ int mpcq_mpc_plants_step_device(mpcq_ctx *c, int nx, int s_rows, const double *A
 {
     int rc = check_generic_dims(c);
     if (rc) return rc;
+    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal("mpcq_mpc_plants_step_device"));
     const int n = c->dims.n, m = c->dims.m;
     if (nx <= 0 || nx > 8 || s_rows < 0) return fail(MPCQ_ERR_ARG, "plants_step: 1 <= nx <= 8, s_rows >= 0");
     if (m != 2 * n || n > 32) return fail(MPCQ_ERR_ARG, "plants_step: n = N <= 32, m = 2N (ModelPredictiveControlAPI.cpp:47-48)");
@@ -1969,6 +2087,7 @@ int mpcq_mimo_setup_plants_device(mpcq_ctx *c, int nx, int nu, int ny, int s_row
 {
     int rc = check_ctx(c, kNone);
     if (rc) return rc;
+    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal("mpcq_mimo_setup_plants_device"));
     if ((rc = materialize_xy(c))) return rc;  // (the operator blocks below replace the tile images' role)
     const int n = c->dims.n, m = c->dims.m;
     if (nu != 1 && nu != 2 && nu != 4) return fail(MPCQ_ERR_ARG, "mimo: n_u must be 1, 2 or 4");
@@ -2035,6 +2154,7 @@ int mpcq_mimo_step_device(mpcq_ctx *c, const double *X, double *U, const double 
 {
     int rc = check_ctx(c, kNone);
     if (rc) return rc;
+    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal("mpcq_mimo_step_device"));
     if ((rc = materialize_xy(c))) return rc;  // (a pending lazy x, y first: the kernel below rewrites the state)
     if (c->mode != mpcq_ctx::Mode::Mimo) return fail(MPCQ_ERR_ORDER, "mpcq_mimo_setup_plants_device has not succeeded");
     if (!X || !U) return fail(MPCQ_ERR_ARG, "null X/U");

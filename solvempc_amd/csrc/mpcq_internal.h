@@ -395,8 +395,32 @@ struct PlantStepArgs {
 };
 }  // namespace mpcq
 
+namespace mpcq {
+// Arguments of polish_kernel (mpcq_polish.hip): OSQP's solution polishing, one QP per wave, fp64.
+struct PolishArgs {
+    int batch, n, m, nc, mc;
+    int shared;                 // 1: every QP uses plant 0
+    int is_f32;                 // the warm state is float (MPCQ_F32 contexts), else double
+    size_t ops_stride;
+    const double *ops;          // [plant] OpsLayout(nc, mc): W, Winv, D, E, Dinv, Einv, c
+    const double *P, *A;        // [plant] n*n (upper triangle read), m*n: the unscaled setup data
+    const double *q, *l, *u;    // [batch] n, m, m: this solve's unscaled data
+    void *xs, *zs, *ys;         // warm state [batch][nc], [batch][mc] x 2 (read; written where polish succeeds)
+    const int *status;          // [batch] the ADMM's status: only MPCQ_SOLVED QPs are polished
+    double *x, *y;              // [batch] n, m: the published ADMM solution, overwritten where polish succeeds
+    double *U;                  // MPC step: U += x[0] for every SOLVED QP (null otherwise)
+    int *pol_status, *pol_nact; // [batch] OSQP status_polish (1, -1, 0), rows of the reduced system
+    double *pol_res;            // [batch][2] primal, dual residual of the returned solution (NaN: not performed)
+    double delta;
+    int refine, scaled_termination;
+};
+}  // namespace mpcq
+
 // Launchers (extern "C" so the host library links them without templates).
 extern "C" {
+// OSQP polish of every SOLVED QP (mpcq_polish.hip; n <= 32, m <= 64): 0 launched, -1 unsupported shape,
+// -2 HIP error (*err).  cus: compute units of the device (grid size).
+int mpcq_internal_polish_launch(const mpcq::PolishArgs *a, int cus, hipStream_t s, hipError_t *err);
 int mpcq_internal_setup_launch(const mpcq::SetupArgs *args, hipStream_t stream);
 int mpcq_internal_setup_wave_launch(const mpcq::SetupArgs *args, hipStream_t stream);
 // Per-plant setup with the direct inverse M(rho)^-1 (mpcq_setup_wave.hip; n <= 32, m <= 64).

@@ -182,7 +182,7 @@ __device__ __forceinline__ void wave_solve_one(const AdmmArgs<T> &a, int nc, int
         for (int t = 0; t < 8; t++)
             if (t < a.nx) Xv[t] = a.X[(size_t)b * a.nx + t];
     }
-    if (a.mpc_u) Uv = a.U[b];
+    if (a.mpc || a.mpc_u) Uv = a.U[b];  // (the front end reads U; mpc_u alone: only U += x(0))
     T qh = T(0);
     if (ln) {
         double qk;

@@ -359,3 +359,23 @@ def flops_mimo_dense(N: int, nx: int, nu: int, ny: int, iters, check: int = 25) 
     it = np.asarray(iters, dtype=np.float64)
     setup = 2 * n * n * (N * ny) + 30 * (n * n + n * m) + 2 * n * n * m + n ** 3 / 3 + n * n
     return setup + it * (4 * n * m + 2 * n * n + 9 * m + 6 * n) + np.floor(it / check) * (4 * n * m + 2 * n * n + 6 * m + 4 * n)
+
+
+def flops_polish(n: int, n_active: int, refine: int = 3) -> int:
+    """FLOPs of one QP's polish solve as mpcq_polish.hip performs it (factorisation, solve, refinement; the
+    residual evaluations and the projection around them are not counted).  Left-looking Cholesky of an N x N
+    matrix: column k costs 2k per row below and on the diagonal, one scaling per row below, a square root
+    and a reciprocal: chol(N) = sum_k [2k (N - k) + (N - k - 1) + 2].  Both triangular solves of an N x N
+    factor: solve(N) = 2 N^2.  With mr = n_active rows in the reduced system:
+      factorisation  chol(n) + mr n^2 (V = L^-1 A_red') + n mr (mr + 1) (S = delta I + V V') + chol(mr)
+      one KKT solve  2 solve(n) + solve(mr) + 4 n mr (A_red t, A_red' nu) + mr
+      one refinement step  2 n^2 + 4 n mr (b - K s) + n + mr (s += ds) + one KKT solve."""
+    n, mr = int(n), int(n_active)
+
+    def chol(N):
+        return sum(2 * k * (N - k) + (N - k - 1) + 2 for k in range(N))
+
+    fact = chol(n) + mr * n * n + n * mr * (mr + 1) + chol(mr)
+    kkt = 4 * n * n + 2 * mr * mr + 4 * n * mr + mr
+    step = 2 * n * n + 4 * n * mr + n + mr + kkt
+    return fact + kkt + int(refine) * step
