@@ -30,6 +30,9 @@
 #ifndef MPCQ_REM4
 #define MPCQ_REM4 1  // build switch for A/B: 0 runs the remainder tile as a full 16x16x4 tile
 #endif
+#ifndef MPCQ_REM4D
+#define MPCQ_REM4D 1  // build switch for A/B: 0 runs the f64 remainder rows (n = 20: rows 16-19) as a padded 16x16x4 tile
+#endif
 #ifndef MPCQ_PK
 #define MPCQ_PK 1  // build switch for A/B: 0 runs the f32 plain iterations on scalar VALU ops
 #endif
@@ -49,6 +52,14 @@ template <> struct Mf<double> {
     static __device__ __forceinline__ acc mma(double a, double b, acc c)
     {
         return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+    }
+    // v_mfma_f64_4x4x4_4b_f64, the four blocks as the four column quads of the wave's 16 QPs: with a =
+    // A[i0 + (c & 3)][4 s + g] and b the iterate register s (x[4 s + g] of column c) in lane (g, c), the
+    // result is row i0 + g of column c: one register of a tile-layout vector, no lane exchange (measured: about a
+    // quarter of a 16x16x4's cycles; tools/mfma_valu_bench.cpp checks the mapping and the cost)
+    static __device__ __forceinline__ double mma4(double a, double b, double c)
+    {
+        return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
     }
 };
 
@@ -225,6 +236,15 @@ __device__ __forceinline__ float rem_reduce(const Mf<float>::acc &p)
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);                // row g
 }
 
+// The lane whose 16x16x4 A fragment (tile t, k-step s) holds the remainder MFMA's fragment of lane (g, c),
+// chain j (rows 4 j .. 4 j + 3 of the tile): A[16 t + 4 j + (c & 3)][4 s + g].  Image row i holds logical row
+// arow(i): f32 4 (i & 3) + (i >> 2) (one chain only), f64 i.
+template <typename T> __device__ __forceinline__ int rem_lane(int lane, int j = 0)
+{
+    if constexpr (std::is_same<T, float>::value) return (lane & 48) | ((lane & 3) << 2);
+    else return (lane & 48) | (4 * j + (lane & 3));
+}
+
 // Optional accumulator init of the products below: a [G][4 NTO] array, or nullptr (a compile-time choice:
 // a runtime null test on a private array's address cannot fold -- private address 0 is valid -- and would
 // keep the array in scratch memory)
@@ -237,9 +257,11 @@ template <typename T, typename IT> __device__ __forceinline__ T init_el(IT p, in
 
 // The same product for G independent 16-QP groups of one wave: every A operand read from LDS feeds
 // G MFMAs, and the G accumulator chains interleave (more independent work per wave).
-// REM (f32, the last tile holds 4 real rows): that tile on v_mfma_f32_4x4x1_16b, its A fragment read
-// from the 16x16x4 image's lane (g, 4 (c & 3)) (see reg_mv), then rem_reduce; init added after it.
-template <typename T, int G, int NTO, int KS, int KSP, int XN, bool REM = false, typename IT = std::nullptr_t>
+// REM (the last tile holds REM < 4 real registers, i.e. 4 REM real rows; f32: REM = 1 only): that tile on the
+// 4-row MFMA, its A fragment read from the 16x16x4 image's lane rem_lane (see reg_mv).  f32:
+// v_mfma_f32_4x4x1_16b, then rem_reduce, init added after it.  f64: REM chains of v_mfma_f64_4x4x4_4b, each
+// started from its init element and ending as the register itself.
+template <typename T, int G, int NTO, int KS, int KSP, int XN, int REM = 0, typename IT = std::nullptr_t>
 __device__ __forceinline__ void tile_mv_g(const T *__restrict__ im, const T (&x)[G][XN], T (&y)[G][4 * NTO],
                                           int lane, IT init)
 {
@@ -247,32 +269,46 @@ __device__ __forceinline__ void tile_mv_g(const T *__restrict__ im, const T (&x)
     constexpr int VEC = 16 / sizeof(T);
     constexpr int NG = (KS + VEC - 1) / VEC;
     constexpr int NF = REM ? NTO - 1 : NTO;
-    static_assert(!REM || std::is_same<T, float>::value, "4x4x1 remainder tile: f32 only");
+    constexpr bool F64 = std::is_same<T, double>::value;
+    constexpr bool REMF = REM > 0 && !F64, REMD = REM > 0 && F64;
+    constexpr int NM = NF + REM;  // A fragments per k-step: full tiles, then the remainder's
+    static_assert(REM >= 0 && REM < 4 && (F64 || REM <= 1), "remainder: 1 register (f32), 1-3 (f64)");
     typedef T vec __attribute__((ext_vector_type(VEC)));
     im = fresh_ptr(im);
-    vec opnd[NTO][NG];
+    vec opnd[NM][NG];
 #pragma unroll
-    for (int t = 0; t < NTO; t++) {
-        const int ln = (REM && t == NF) ? ((lane & 48) | ((lane & 3) << 2)) : lane;
+    for (int t = 0; t < NM; t++) {
+        const int ln = t >= NF ? rem_lane<T>(lane, t - NF) : lane;
 #pragma unroll
-        for (int q = 0; q < NG; q++) opnd[t][q] = *(const vec *)(im + TileLayout::at(KSP, VEC, t, q * VEC, ln));
+        for (int q = 0; q < NG; q++)
+            opnd[t][q] = *(const vec *)(im + TileLayout::at(KSP, VEC, t < NF ? t : NF, q * VEC, ln));
     }
     A acc[G][NTO];
+    T racc[G][REMD ? REM : 1];  // f64 remainder chains
 #pragma unroll
-    for (int gi = 0; gi < G; gi++)
+    for (int gi = 0; gi < G; gi++) {
 #pragma unroll
         for (int t = 0; t < NTO; t++)
 #pragma unroll
             for (int r = 0; r < 4; r++) acc[gi][t][r] = (kHasInit<IT> && t < NF) ? init_el<T>(init, gi, 4 * t + r) : T(0);
 #pragma unroll
+        for (int j = 0; j < (REMD ? REM : 1); j++) racc[gi][j] = REMD ? init_el<T>(init, gi, 4 * NF + j) : T(0);
+    }
+#pragma unroll
     for (int s = 0; s < KS; s++)
 #pragma unroll
-        for (int t = 0; t < NTO; t++)
+        for (int t = 0; t < NM; t++)
 #pragma unroll
             for (int gi = 0; gi < G; gi++) {
-                if constexpr (REM) {
+                if constexpr (REMF) {
                     if (t == NF) {
                         acc[gi][t] = __builtin_amdgcn_mfma_f32_4x4x1f32(opnd[t][s / VEC][s % VEC], x[gi][s], acc[gi][t], 0, 0, 0);
+                        continue;
+                    }
+                }
+                if constexpr (REMD) {
+                    if (t >= NF) {
+                        racc[gi][t - NF] = Mf<T>::mma4(opnd[t][s / VEC][s % VEC], x[gi][s], racc[gi][t - NF]);
                         continue;
                     }
                 }
@@ -284,7 +320,7 @@ __device__ __forceinline__ void tile_mv_g(const T *__restrict__ im, const T (&x)
         for (int t = 0; t < NTO; t++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                if constexpr (REM) {
+                if constexpr (REMF) {
                     if (t == NF) {
                         if (r == 0) {
                             const T v = rem_reduce(acc[gi][t]);
@@ -295,6 +331,12 @@ __device__ __forceinline__ void tile_mv_g(const T *__restrict__ im, const T (&x)
                         continue;
                     }
                 }
+                if constexpr (REMD) {
+                    if (t == NF) {
+                        y[gi][4 * t + r] = r < REM ? racc[gi][r < REM ? r : 0] : T(0);
+                        continue;
+                    }
+                }
                 y[gi][4 * t + r] = acc[gi][t][r];
             }
 }
@@ -302,40 +344,60 @@ __device__ __forceinline__ void tile_mv_g(const T *__restrict__ im, const T (&x)
 // Products with the A operand held in VGPRs (one f32/f64 register per lane per tile and k-step: the
 // 16x16x4 A fragment, lane l = A[16 t + arow(l & 15)][4 s + (l >> 4)]), for the paired hot loop:
 // y = init + M1 x1 (+ M2 x2), the NTO x G accumulator chains interleaved k-step by k-step.
-// REM (f32, n = 16 (NTO - 1) + 4, e.g. N = 20): the last tile holds 4 real rows, so it runs as
-// v_mfma_f32_4x4x1_16b (16 blocks of 4 rows x 4 QPs, one k each: a quarter of a 16x16x4's issue
-// cycles) with the A fragment lane (g, c) = A[16 (NTO - 1) + (c & 3)][4 s + g] and the iterate
-// register as B operand, then rem_reduce; its init is added after the reduction.
-// RMODE (REM only) defers the remainder tile's lane reduction across two products: 1 = leave its
+// REM (n = 16 (NTO - 1) + 4 REM, e.g. N = 20: REM = 1; the stacked [B~; S] of N = 20: REM = 2): the last
+// tile holds REM < 4 real registers and runs on the 4-row MFMA with the iterate register as B operand.
+// f32 (REM = 1): v_mfma_f32_4x4x1_16b (16 blocks of 4 rows x 4 QPs, one k each: a quarter of a 16x16x4's
+// issue cycles) with the A fragment lane (g, c) = A[16 (NTO - 1) + (c & 3)][4 s + g], then rem_reduce; its
+// init is added after the reduction.
+// f64: REM chains of v_mfma_f64_4x4x4_4b (Mf<double>::mma4), chain j with the A fragment m[NTO - 1 + j]
+// = A[16 (NTO - 1) + 4 j + (c & 3)][4 s + g] (load with rem_lane); a chain starts from its init element
+// and ends as output register 4 (NTO - 1) + j: no reduction, the other registers of that tile are zero.
+// RMODE (f32 REM only) defers the remainder tile's lane reduction across two products: 1 = leave its
 // 4x4x1 partial sums unreduced in rem[] and put init's remainder element (not the product's) into y;
 // 2 = start the remainder chain from rem[] (the partials of a mode-1 product), reduce, add init.
-template <typename T, int G, int NTO, int KS, int XN, bool TWO, int XN2, bool REM = false, int RMODE = 0,
+// A fragments per k-step of reg_mv's operator arrays: the full tiles, then (f64) one per remainder chain
+template <typename T, int REM, int NTO>
+constexpr int kRegMvTiles = (REM > 0 && std::is_same<T, double>::value) ? NTO - 1 + REM : NTO;
+template <typename T, int G, int NTO, int KS, int XN, bool TWO, int XN2, int REM = 0, int RMODE = 0,
           typename IT = std::nullptr_t>
-__device__ __forceinline__ void reg_mv(const T (&m1)[NTO][KS], const T (&x1)[G][XN], const T (&m2)[NTO][KS],
-                                       const T (&x2)[G][XN2], T (&y)[G][4 * NTO], IT init,
-                                       typename Mf<T>::acc *rem = nullptr)
+__device__ __forceinline__ void reg_mv(const T (&m1)[kRegMvTiles<T, REM, NTO>][KS], const T (&x1)[G][XN],
+                                       const T (&m2)[kRegMvTiles<T, REM, NTO>][KS], const T (&x2)[G][XN2],
+                                       T (&y)[G][4 * NTO], IT init, typename Mf<T>::acc *rem = nullptr)
 {
     using A = typename Mf<T>::acc;
     constexpr int NF = REM ? NTO - 1 : NTO;  // full 16-row tiles
-    static_assert(!REM || std::is_same<T, float>::value, "4x4x1 remainder tile: f32 only");
-    static_assert(RMODE == 0 || REM, "deferred remainder reduction: remainder tile only");
+    constexpr bool F64 = std::is_same<T, double>::value;
+    constexpr bool REMF = REM > 0 && !F64, REMD = REM > 0 && F64;
+    constexpr int NM = kRegMvTiles<T, REM, NTO>;
+    static_assert(REM >= 0 && REM < 4 && (F64 || REM <= 1), "remainder: 1 register (f32), 1-3 (f64)");
+    static_assert(RMODE == 0 || REMF, "deferred remainder reduction: f32 remainder tile only");
     A acc[G][NTO];
+    T racc[G][REMD ? REM : 1];  // f64 remainder chains
 #pragma unroll
-    for (int gi = 0; gi < G; gi++)
+    for (int gi = 0; gi < G; gi++) {
 #pragma unroll
         for (int t = 0; t < NTO; t++)
 #pragma unroll
             for (int r = 0; r < 4; r++)
                 acc[gi][t][r] = (kHasInit<IT> && t < NF) ? init_el<T>(init, gi, 4 * t + r)
                                                          : ((RMODE == 2 && t == NF) ? rem[gi][r] : T(0));
-    auto step = [&](const T (&m)[NTO][KS], auto &x, int s) {
 #pragma unroll
-        for (int t = 0; t < NTO; t++)
+        for (int j = 0; j < (REMD ? REM : 1); j++) racc[gi][j] = REMD ? init_el<T>(init, gi, 4 * NF + j) : T(0);
+    }
+    auto step = [&](const T (&m)[NM][KS], auto &x, int s) {
+#pragma unroll
+        for (int t = 0; t < NM; t++)
 #pragma unroll
             for (int gi = 0; gi < G; gi++) {
-                if constexpr (REM) {
+                if constexpr (REMF) {
                     if (t == NF) {
                         acc[gi][t] = __builtin_amdgcn_mfma_f32_4x4x1f32(m[t][s], x[gi][s], acc[gi][t], 0, 0, 0);
+                        continue;
+                    }
+                }
+                if constexpr (REMD) {
+                    if (t >= NF) {
+                        racc[gi][t - NF] = Mf<T>::mma4(m[t][s], x[gi][s], racc[gi][t - NF]);
                         continue;
                     }
                 }
@@ -354,14 +416,14 @@ __device__ __forceinline__ void reg_mv(const T (&m1)[NTO][KS], const T (&x1)[G][
         for (int t = 0; t < NTO; t++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                if constexpr (REM && RMODE == 1) {
+                if constexpr (REMF && RMODE == 1) {
                     if (t == NF) {
                         if (r == 0) rem[gi] = acc[gi][t];
                         y[gi][4 * t + r] = (kHasInit<IT> && r == 0) ? init_el<T>(init, gi, 4 * t) : T(0);
                         continue;
                     }
                 }
-                if constexpr (REM) {
+                if constexpr (REMF) {
                     if (t == NF) {
                         if (r == 0) {
                             const T v = rem_reduce(acc[gi][t]);
@@ -369,6 +431,12 @@ __device__ __forceinline__ void reg_mv(const T (&m1)[NTO][KS], const T (&x1)[G][
                         } else {
                             y[gi][4 * t + r] = T(0);
                         }
+                        continue;
+                    }
+                }
+                if constexpr (REMD) {
+                    if (t == NF) {
+                        y[gi][4 * t + r] = r < REM ? racc[gi][r < REM ? r : 0] : T(0);
                         continue;
                     }
                 }
@@ -531,7 +599,12 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
     constexpr int KNR = PAIRED ? KN : 1, NTR = PAIRED ? NT : 1;
     // f32 paired loop with n = 16 (NT - 1) + 4 (N = 20): the last tile's 4 rows on the 4x4x1 MFMA
     constexpr bool REM4F = PAIRED && KN % 4 == 1 && NT > 1 && MPCQ_REM4;  // (the fp32 loop's remainder tile)
-    constexpr bool REM4 = REM4F && std::is_same<T, float>::value;
+    // f64 (MPCQ_REM4D): the same rows on the f64 4x4x4 MFMA, in every n-row product of the paired kernel; REM4
+    // is the remainder of T's own products, REM4D that of the products that only the f64 kernel converts
+    constexpr bool REM4D = PAIRED && KN % 4 == 1 && NT > 1 && MPCQ_REM4D && std::is_same<T, double>::value;
+    constexpr bool REM4 = (REM4F && std::is_same<T, float>::value) || REM4D;
+    // the stacked [B~; S] product (8 KN rows): its last tile's real registers (N = 20: 2) as 4x4x4 chains
+    constexpr int STKR = (REM4D && L.NBS > 0) ? (2 * KN) % 4 : 0;
     const int n = a.n, m = a.m;
     const int ncs = NCP, mcs = MCP;                // state row strides (ctx nc, mc)
     const PlantOps<T> op = a.ops;                  // shared plant: block 0
@@ -713,7 +786,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
     MPCQ_PRO_MARK(14);
 
     // g = W' q^ (the q-part of the KKT right-hand side in the W-basis)
-    tile_mv_g<T, G, NT, KN, KNP>(img + L.Wt, qh, gv, lane, nullptr);
+    tile_mv_g<T, G, NT, KN, KNP, NS, REM4D>(img + L.Wt, qh, gv, lane, nullptr);
 #pragma unroll
     for (int gi = 0; gi < G; gi++)
 #pragma unroll
@@ -952,9 +1025,9 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
         const T *im = fresh_ptr((const T *)img);
 #pragma unroll
         for (int t = 0; t < NTR; t++) {
-            // REM4: the 4x4x1 tile's fragment lane (g, c) is the 16x16x4 image's lane (g, 4 (c & 3))
-            // (image row i holds logical row arow(i) = 4 (i & 3) + (i >> 2))
-            const int ln = (REM4 && t == NTR - 1) ? ((lane & 48) | ((lane & 3) << 2)) : lane;
+            // REM4: the remainder MFMA's fragment lane (g, c) is the 16x16x4 image's lane rem_lane: f32
+            // (g, 4 (c & 3)) (image row i holds logical row arow(i) = 4 (i & 3) + (i >> 2)), f64 (g, c & 3)
+            const int ln = (REM4 && t == NTR - 1) ? rem_lane<T>(lane) : lane;
 #pragma unroll
             for (int k = 0; k < KNR; k++) {
                 rS[t][k] = im[L.S + TileLayout::at(KNP, VEC, t, k, ln)];
@@ -1053,18 +1126,25 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
     // x' = eta' + (1 - alpha) x'_old, so the next -g + S x' = (1 - alpha)(-g + S x'_old) + alpha (-g) + S eta':
     // the product's S rows start from that (a contraction by |1 - alpha| < 1: rounding does not build up).
     constexpr int NBR = NBS > 0 ? NBS : 1;
-    auto load_regs_stk = [&](T (&rBt)[NTR][KNR], T (&rBS)[NBR][KNR]) {
+    // (MPCQ_REM4D: the last tile of B~' as one 4x4x4 chain; the last tile of [B~; S], whose STKR real
+    // registers are S rows 16 (NBR - 1) - 4 KN .., as STKR chains: fragments NBR - 1 + j, read from the same image)
+    constexpr int NBF = STKR > 0 ? NBR - 1 : NBR, NBM = NBF + STKR;  // full tiles, fragments per k-step
+    auto load_regs_stk = [&](T (&rBt)[NTR][KNR], T (&rBS)[NBM][KNR]) {
         const T *im = fresh_ptr((const T *)img);
 #pragma unroll
-        for (int t = 0; t < NTR; t++)
+        for (int t = 0; t < NTR; t++) {
+            const int ln = (REM4D && t == NTR - 1) ? rem_lane<T>(lane) : lane;
 #pragma unroll
-            for (int k = 0; k < KNR; k++) rBt[t][k] = im[L.Bt + TileLayout::at(KBT, VEC, t, k, lane)];
+            for (int k = 0; k < KNR; k++) rBt[t][k] = im[L.Bt + TileLayout::at(KBT, VEC, t, k, ln)];
+        }
 #pragma unroll
-        for (int t = 0; t < NBR; t++)
+        for (int t = 0; t < NBM; t++) {
+            const int ln = t >= NBF ? rem_lane<T>(lane, t - NBF) : lane;
 #pragma unroll
-            for (int k = 0; k < KNR; k++) rBS[t][k] = im[L.BS + TileLayout::at(KNP, VEC, t, k, lane)];
+            for (int k = 0; k < KNR; k++) rBS[t][k] = im[L.BS + TileLayout::at(KNP, VEC, t < NBF ? t : NBF, k, ln)];
+        }
     };
-    auto piter_stk = [&](const T (&rBt)[NTR][KNR], const T (&rBS)[NBR][KNR], T (&sx)[G][NS], const T (&adk)[G][KNR],
+    auto piter_stk = [&](const T (&rBt)[NTR][KNR], const T (&rBS)[NBM][KNR], T (&sx)[G][NS], const T (&adk)[G][KNR],
                          const T (&agv)[G][KNR]) {
         if constexpr (NBS > 0) {
             T wt[G][KNR];
@@ -1074,7 +1154,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
                 for (int s = 0; s < KN; s++)
                     wt[gi][s] = rho[gi] * ((z[gi][s] - y[gi][s]) - (z[gi][s + KN] - y[gi][s + KN]));
             T xi[G][NS];
-            reg_mv<T, G, NT, KN, KNR, false, KNR>(rBt, wt, rBt, wt, xi, sx);  // xi = (-g + S x') + B~' w~
+            reg_mv<T, G, NT, KN, KNR, false, KNR, REM4D>(rBt, wt, rBt, wt, xi, sx);  // xi = (-g + S x') + B~' w~
             T ini[G][4 * NBR];  // z~ rows from 0, S rows from (1 - alpha)(-g + S x'_old) + alpha (-g)
 #pragma unroll
             for (int gi = 0; gi < G; gi++)
@@ -1089,7 +1169,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
                     xs[gi][s] = tt_fma(oma, xs[gi][s], xi[gi][s]);  // x' = alpha eta + (1 - alpha) x'
                 }
             T out[G][4 * NBR];
-            reg_mv<T, G, NBR, KN, NS, false, KNR>(rBS, xi, rBS, wt, out, ini);  // [alpha z~_top; next -g + S x']
+            reg_mv<T, G, NBR, KN, NS, false, KNR, STKR>(rBS, xi, rBS, wt, out, ini);  // [alpha z~_top; next -g + S x']
 #pragma unroll
             for (int gi = 0; gi < G; gi++) {
 #pragma unroll
@@ -1326,10 +1406,10 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
             }
             if constexpr (NBS > 0) {
                 if (it + 1 < nxt) {
-                    T rBt[NTR][KNR], rBS[NBR][KNR];
+                    T rBt[NTR][KNR], rBS[NBM][KNR];
                     load_regs_stk(rBt, rBS);
                     T sx[G][NS], adk[G][KNR], agv[G][KNR];
-                    tile_mv_g<T, G, NT, KN, KNP>(img + L.S, xs, sx, lane, gv);  // -g + S x'
+                    tile_mv_g<T, G, NT, KN, KNP, NS, REM4D>(img + L.S, xs, sx, lane, gv);  // -g + S x'
 #pragma unroll
                     for (int gi = 0; gi < G; gi++) {
 #pragma unroll
@@ -1677,7 +1757,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
             }
             if (!wave_any(anyc)) return;
             T t1[G][NS], ndx[G];
-            tile_mv_g<T, G, NT, KN, KNP>(img + L.W, dx, t1, lane, nullptr);
+            tile_mv_g<T, G, NT, KN, KNP, NS, REM4D>(img + L.W, dx, t1, lane, nullptr);
             const T *D = fresh_ptr((const T *)s_D);
             const T cs = scaled_term ? T(1) : op.cs[0];
             anyc = false;
@@ -1691,7 +1771,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
                 anyc = anyc || cand[gi];
             }
             if (!wave_any(anyc)) return;
-            tile_mv_g<T, G, NT, KN, KNP>(img + L.PW, dx, t1, lane, nullptr);
+            tile_mv_g<T, G, NT, KN, KNP, NS, REM4D>(img + L.PW, dx, t1, lane, nullptr);
             const T *Dinv = fresh_ptr((const T *)s_Dinv);
             anyc = false;
 #pragma unroll
