@@ -197,6 +197,30 @@ int mpcq_mpc_step_device(mpcq_ctx *ctx, const double *X_dev, double *U_dev, doub
 /* Host-memory convenience form of mpcq_mpc_step_device (copies in/out, synchronises). */
 int mpcq_mpc_step(mpcq_ctx *ctx, const double *X, double *U, double xref);
 
+/* ---- per-QP reference trajectories with horizon preview --------------------------------------
+ * The reference drives one plant to one set-point (updateRef :378-380, ref = xref 1); a batch of
+ * controllers has one set-point each, and a tracking controller wants its horizon to see a set-point
+ * change before it arrives.  The condensed QP carries that already (Fr is the full N x N operator), so
+ * these twins of the entry points above take the horizon reference itself.
+ * One controllerStep for every QP with its own horizon reference:
+ *   q_b = Fx X_b + Fu U_b + Fr ref_b,  ref_b[j] = ref_dev[b*ref_stride + j], j = 0..n-1.
+ * ref_stride == 0: one n-vector shared by the batch; otherwise ref_stride >= n.
+ * ref_dev is read-only for the call and must stay valid and unchanged until the solve has finished
+ * on `stream` (later phases of a tile solve re-form q from it, as they do from X).
+ * Arithmetic: q_v = s0 + s1 + s2 with s0, s1 as in mpcq_mpc_step_device and s2 = sum_t Fr[v,t] ref[t]
+ * accumulated in ascending t in fp64, the form of the scalar entry point's row sum, so a reference whose
+ * entries all equal xref reproduces mpcq_mpc_step_device bit for bit on every device path and dtype.
+ * Every path of mpcq_mpc_step_device is served (tile kernel, one QP per wave, one QP per lane), with its
+ * hardest-first order (the key gains -A P^-1 Fr ref_b: still the key of the QP's actual q) and
+ * settings.polish.  q and u are written eagerly on this path (no lazy q/u): mpcq_device_view_get().q and
+ * a following mpcq_solve see this step's q even after the caller has overwritten ref_dev.
+ * Returns MPCQ_ERR_ARG for a null ref or a non-zero stride < n, otherwise as mpcq_mpc_step_device.
+ * Out of scope: mpcq_mpc_plants_step_device and the MIMO entry points (MIMO has yref). */
+int mpcq_mpc_step_ref_device(mpcq_ctx *ctx, const double *X_dev, double *U_dev, const double *ref_dev,
+                             long long ref_stride, void *stream);
+/* Host-memory form (copies in/out, synchronises), as mpcq_mpc_step is to mpcq_mpc_step_device. */
+int mpcq_mpc_step_ref(mpcq_ctx *ctx, const double *X, double *U, const double *ref, long long ref_stride);
+
 /* ---- receding-horizon stream (BASELINE config 5; the solver.cpp loop, solver.cpp:43-74, with the
  * serial plant replaced by a simulated one) ----------------------------------------------------
  * Plant of every QP: X <- Ad X + Bd U + w,  w ~ N(0, noise_std^2 I) drawn from a counter-based
@@ -214,6 +238,18 @@ int mpcq_mpc_simulate_device(mpcq_ctx *ctx, double *X_dev, const double *U_dev, 
 int mpcq_mpc_run_device(mpcq_ctx *ctx, double *X_dev, double *U_dev, double xref, int steps,
                         unsigned long long seed, long long first_qp, long long first_step,
                         double noise_std, void *stream);
+/* mpcq_mpc_run_device with a reference schedule: the control step with absolute index
+ * s = first_step + k uses ref_b[j] = sched_dev[b*sched_stride + min(s + j, sched_len - 1)]
+ * (the last value is held).  sched_stride == 0: one schedule shared by the batch; else >= sched_len.
+ * b is the context's local QP index (a shard passes its own rows).  sched_len >= 1, first_step >= 0.
+ * The window slides inside the one-launch stream kernels (a column or wave starting its step k loads
+ * the window at first_step + k); the per-step graph takes the step from the context's device step
+ * counter, as its captured plant simulation does.  sched_dev must stay valid and unchanged until the
+ * stream has finished.  Afterwards q, u are the last step's.  MPCQ_ERR_ARG: null schedule, sched_len < 1,
+ * a non-zero stride < sched_len, first_step < 0, or settings.polish set (as mpcq_mpc_run_device). */
+int mpcq_mpc_run_ref_device(mpcq_ctx *ctx, double *X_dev, double *U_dev, const double *sched_dev,
+                            int sched_len, long long sched_stride, int steps, unsigned long long seed,
+                            long long first_qp, long long first_step, double noise_std, void *stream);
 /* How the last mpcq_mpc_run_device call ran (benchmarks and tests): MPCQ_STREAM_TILE (one tile-kernel
  * launch), MPCQ_STREAM_WAVE (one one-QP-per-wave launch) or MPCQ_STREAM_GRAPH (per-step launches). */
 #define MPCQ_STREAM_GRAPH 0

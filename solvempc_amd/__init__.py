@@ -204,6 +204,40 @@ class BatchSolver:
         _capi.check(lib().mpcq_mpc_step(self._ctx, _dp(X), _dp(U), float(xref)), "mpcq_mpc_step")
         return U
 
+    # -- per-QP reference trajectories with horizon preview (mpcq_mpc_step_ref*, mpcq_mpc_run_ref_device)
+    def mpc_step_ref(self, X, U, ref) -> np.ndarray:
+        """mpc_step with a horizon reference: ``ref`` of shape (n,) is shared by the batch, (batch, n) is
+        one per QP (q_b = Fx X_b + Fu U_b + Fr ref_b); returns new U."""
+        X = _c64(X).reshape(self.batch, self.nx)
+        U = _c64(U).reshape(self.batch).copy()
+        ref = _c64(ref)
+        if ref.shape == (self.n,):
+            stride = 0
+        elif ref.shape == (self.batch, self.n):
+            stride = self.n
+        else:
+            raise ValueError(f"ref of shape {ref.shape}: ({self.n},) or ({self.batch}, {self.n})")
+        _capi.check(lib().mpcq_mpc_step_ref(self._ctx, _dp(X), _dp(U), _dp(ref), stride), "mpcq_mpc_step_ref")
+        return U
+
+    def mpc_step_ref_device(self, X_ptr: int, U_ptr: int, ref_ptr: int, ref_stride: int,
+                            stream: int | None = None) -> None:
+        """Same on device-resident fp64 buffers: QP b reads ref[b * ref_stride + j], j < n (ref_stride 0: one
+        shared n-vector); the buffer must stay unchanged until the solve has finished.  Asynchronous."""
+        _capi.check(lib().mpcq_mpc_step_ref_device(self._ctx, C.c_void_p(X_ptr), C.c_void_p(U_ptr),
+                                                   C.c_void_p(ref_ptr or 0), int(ref_stride),
+                                                   C.c_void_p(stream or 0)), "mpcq_mpc_step_ref_device")
+
+    def mpc_run_ref_device(self, X_ptr: int, U_ptr: int, sched_ptr: int, sched_len: int, sched_stride: int,
+                           steps: int, seed: int, first_qp: int, first_step: int, noise_std: float,
+                           stream: int) -> None:
+        """mpc_run_device with a reference schedule: control step s = first_step + k of QP b uses
+        ref[j] = sched[b * sched_stride + min(s + j, sched_len - 1)] (sched_stride 0: one shared schedule)."""
+        _capi.check(lib().mpcq_mpc_run_ref_device(self._ctx, C.c_void_p(X_ptr), C.c_void_p(U_ptr),
+                                                  C.c_void_p(sched_ptr or 0), int(sched_len), int(sched_stride),
+                                                  int(steps), seed, first_qp, first_step, float(noise_std),
+                                                  C.c_void_p(stream)), "mpcq_mpc_run_ref_device")
+
     # -- receding-horizon stream (BASELINE config 5): simulated plant + graph-captured control steps
     def mpc_set_plant(self, Ad, Bd) -> None:
         k = self.n_plants

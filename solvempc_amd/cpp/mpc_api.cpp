@@ -295,12 +295,38 @@ void ModelPredictiveControlAPI::setF()
 void ModelPredictiveControlAPI::updateRef(double pos_ref)
 {
     ref = Matrix(1, horizon, pos_ref);
+    ref_trajectory_ = false;
+    if (verbose) std::cout << "[MPC API]\tref: " << ref << std::endl;
+}
+
+// A horizon reference with preview (no counterpart in the reference, which tracks one set-point): `ref` is
+// the trajectory itself and controllerStep steps through mpcq_mpc_step_ref until updateRef(double).
+void ModelPredictiveControlAPI::updateRef(const std::vector<double> &trajectory)
+{
+    if ((int)trajectory.size() != horizon) throw std::invalid_argument("updateRef: the trajectory needs `horizon` values");
+    ref = Matrix(1, horizon);
+    for (int t = 0; t < horizon; t++) ref(t) = trajectory[t];
+    ref_trajectory_ = true;
     if (verbose) std::cout << "[MPC API]\tref: " << ref << std::endl;
 }
 
 bool ModelPredictiveControlAPI::controllerStep()
 {
     t0 += dt;
+    if (ref_trajectory_) {  // the device front end forms q, u from X, U and the trajectory
+        setF();
+        if (!mpc_ops_set_) {
+            if (!solver.setMpcOperators(N_S, Fx.row_major(), Fu.row_major(), Fr.row_major(), Sbar.row_major(),
+                                        Ku.row_major(), W0.row_major()))
+                return false;
+            mpc_ops_set_ = true;
+        }
+        double u = U(0);
+        const bool ok = solver.mpcStepRef(std::vector<double>(X.data(), X.data() + N_S),
+                                          u, std::vector<double>(ref.data(), ref.data() + horizon));
+        U(0) = u;  // receding horizon (:105): moved only when SOLVED
+        return ok;
+    }
     updateRef(xref);
     setF();
     setUpperBound();

@@ -44,6 +44,9 @@ public:
     void setF();
     void setUpperBound();
     void updateRef(double pos_ref);
+    // A horizon reference of `horizon` values (preview; no counterpart in the reference): controllerStep
+    // then runs mpcq_mpc_step_ref; updateRef(double) returns to the scalar path.
+    void updateRef(const std::vector<double> &trajectory);
     void setLL();
     void setLu();
     bool controllerStep();
@@ -73,6 +76,7 @@ private:
     void transformations_for_dump(mpcq::Matrix &CAB, mpcq::Matrix &CAiB, mpcq::Matrix &CAB_full, mpcq::Matrix &Su_full,
                                   mpcq::Matrix &Su_full1) const;
     bool condensed_ = false;
+    bool ref_trajectory_ = false, mpc_ops_set_ = false;
     int device_;
 };
 

@@ -190,4 +190,27 @@ bool Solver::solve()
     return status_ == MPCQ_SOLVED;
 }
 
+bool Solver::setMpcOperators(int nx, const Vector &Fx, const Vector &Fu, const Vector &Fr, const Vector &Sbar,
+                             const Vector &Ku, const Vector &W0)
+{
+    const int n = data_.n_, m = data_.m_;
+    if (!ctx_ || nx <= 0 || (int)Fx.size() != n * nx || (int)Fu.size() != n || (int)Fr.size() != n * n ||
+        (int)Sbar.size() != m * nx || (int)Ku.size() != m || (int)W0.size() != m)
+        return fail("setMpcOperators");
+    if (mpcq_mpc_set_operators(ctx_, nx, Fx.data(), Fu.data(), Fr.data(), Sbar.data(), Ku.data(), W0.data()) != MPCQ_OK)
+        return fail("mpcq_mpc_set_operators");
+    mpc_nx_ = nx;
+    return true;
+}
+
+bool Solver::mpcStepRef(const Vector &X, double &U, const Vector &ref)
+{
+    if (!ctx_ || mpc_nx_ <= 0 || (int)X.size() != mpc_nx_ || (int)ref.size() != data_.n_) return fail("mpcStepRef");
+    if (mpcq_mpc_step_ref(ctx_, X.data(), &U, ref.data(), 0) != MPCQ_OK) return fail("mpcq_mpc_step_ref");
+    if (mpcq_get_info(ctx_, &status_, &iter_, &rho_) != MPCQ_OK) return fail("mpcq_get_info");
+    if (mpcq_get_solution(ctx_, x_.data()) != MPCQ_OK) return fail("mpcq_get_solution");
+    if (data_.m_ > 0 && mpcq_get_dual(ctx_, y_.data()) != MPCQ_OK) return fail("mpcq_get_dual");
+    return status_ == MPCQ_SOLVED;
+}
+
 }  // namespace mpcq

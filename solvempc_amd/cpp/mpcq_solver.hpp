@@ -113,6 +113,13 @@ public:
     bool updateLowerBound(const Vector &l);
     bool updateBounds(const Vector &l, const Vector &u);
     bool solve();                               // osqp_solve; true iff OSQP_SOLVED
+    // Condensed-MPC front end of the C ABI (no osqp-eigen counterpart): the operators (row-major: Fx n*nx,
+    // Fu n, Fr n*n, Sbar m*nx, Ku m, W0 m), then one controllerStep with a horizon reference of n values
+    // (mpcq_mpc_step_ref: q = Fx X + Fu U + Fr ref, u = W0 + Sbar X + Ku U, solve, U += x[0] when SOLVED);
+    // true iff OSQP_SOLVED, the results as after solve()
+    bool setMpcOperators(int nx, const Vector &Fx, const Vector &Fu, const Vector &Fr, const Vector &Sbar,
+                         const Vector &Ku, const Vector &W0);
+    bool mpcStepRef(const Vector &X, double &U, const Vector &ref);
     const Vector &getSolution() const { return x_; }
     const Vector &getDualSolution() const { return y_; }
     int getStatus() const { return status_; }
@@ -127,7 +134,7 @@ private:
     Data data_;
     mpcq_ctx *ctx_ = nullptr;
     Vector x_, y_, E_, l_scaled_;
-    int status_ = MPCQ_UNSOLVED, iter_ = 0;
+    int status_ = MPCQ_UNSOLVED, iter_ = 0, mpc_nx_ = 0;
     double rho_ = 0.0;
     std::string err_;
 };

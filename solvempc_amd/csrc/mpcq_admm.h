@@ -147,9 +147,21 @@ struct LdsLayout {
 // otherwise the scheduler spends registers on ILP up to the 512 a 64-lane block permits.
 template <typename T> constexpr int kWavesPerSimd = sizeof(T) == 4 ? 3 : 2;
 
+// A translation unit that defines MPCQ_LANE_REF before this header (mpcq_admm_ref_*.hip) compiles the same
+// kernel text as admm_lane_ref_kernel, whose front end reads the QP's own horizon reference (RefArgs, a second
+// kernel argument) in place of xref 1; the scalar units' admm_lane_kernel keeps its name, arguments and code.
+#ifdef MPCQ_LANE_REF
+#define MPCQ_LANE_KERNEL admm_lane_ref_kernel
+#define MPCQ_LANE_REF_PARAM , RefArgs ref
+#define MPCQ_LANE_REF_ARG(r) , *(r)
+#else
+#define MPCQ_LANE_KERNEL admm_lane_kernel
+#define MPCQ_LANE_REF_PARAM
+#define MPCQ_LANE_REF_ARG(r)
+#endif
 template <typename T, int NC, int MC, bool SHARED, bool ALL_INEQ, bool LFREE>
 __global__ __launch_bounds__(64) 
-void admm_lane_kernel(AdmmArgs<T> a)
+void MPCQ_LANE_KERNEL(AdmmArgs<T> a MPCQ_LANE_REF_PARAM)
 {
     constexpr OpsLayout L = OpsLayout::make(NC, MC);
     using LL = LdsLayout<T, NC, MC, LFREE>;
@@ -198,7 +210,13 @@ void admm_lane_kernel(AdmmArgs<T> a)
                     for (int t = 0; t < 8; t++)
                         if (t < a.nx) s0 += fx[t] * Xv[t];
                     const double s1 = a.Fu[(SHARED ? 0 : (size_t)b * n) + k] * Uv;
+#ifdef MPCQ_LANE_REF
+                    const double *rrow = ref.row(b);
+                    const long long r0 = ref.first(0);
+                    for (int t = 0; t < n; t++) s2 += fr[t] * ref.at(rrow, r0, t);
+#else
                     for (int t = 0; t < n; t++) s2 += fr[t] * a.xref;
+#endif
                     qk = s0 + s1 + s2;
                     a.q_out[(size_t)b * n + k] = qk;
                 } else {
@@ -497,16 +515,17 @@ __global__ __launch_bounds__(64) void warm_start_kernel(AdmmArgs<T> a, int nc, i
 
 // ---------------------------------------------------------------------------------------------
 template <typename T, int NC, int MC>
-static int launch_cap(const AdmmArgs<T> &a, hipStream_t s)
+static int launch_cap(const AdmmArgs<T> &a, hipStream_t s, const RefArgs *ref = nullptr)
 {
     const dim3 grid((a.batch + 63) / 64), block(64);
     // Specialisations: shared plant (scalar operands) x all-inequality rows x lower bounds all -inf.
+    // (ref: the REF units' second kernel argument, MPCQ_LANE_REF_ARG; nothing in the scalar ones)
     if (a.shared && a.all_ineq && a.lower_free)
-        hipLaunchKernelGGL((admm_lane_kernel<T, NC, MC, true, true, true>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((MPCQ_LANE_KERNEL<T, NC, MC, true, true, true>), grid, block, 0, s, a MPCQ_LANE_REF_ARG(ref));
     else if (a.shared)
-        hipLaunchKernelGGL((admm_lane_kernel<T, NC, MC, true, false, false>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((MPCQ_LANE_KERNEL<T, NC, MC, true, false, false>), grid, block, 0, s, a MPCQ_LANE_REF_ARG(ref));
     else
-        hipLaunchKernelGGL((admm_lane_kernel<T, NC, MC, false, false, false>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((MPCQ_LANE_KERNEL<T, NC, MC, false, false, false>), grid, block, 0, s, a MPCQ_LANE_REF_ARG(ref));
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -514,9 +533,9 @@ static int launch_cap(const AdmmArgs<T> &a, hipStream_t s)
 #define MPCQ_CAPS(X) X(8, 16) X(16, 32) X(20, 40) X(32, 64)
 
 template <typename T>
-static int launch_any(const AdmmArgs<T> &a, int nc, int mc, hipStream_t s)
+static int launch_any(const AdmmArgs<T> &a, int nc, int mc, hipStream_t s, const RefArgs *ref = nullptr)
 {
-#define MPCQ_TRY(NC_, MC_) if (nc == NC_ && mc == MC_) return launch_cap<T, NC_, MC_>(a, s);
+#define MPCQ_TRY(NC_, MC_) if (nc == NC_ && mc == MC_) return launch_cap<T, NC_, MC_>(a, s, ref);
     MPCQ_CAPS(MPCQ_TRY)
 #undef MPCQ_TRY
     return -1;

@@ -1,0 +1,11 @@
+// solvempc_amd/csrc/mpcq_admm_ref_f64.hip — f64 instantiations of the lane kernel's REF variant (per-QP horizon
+// references, RefArgs: mpcq_mpc_step_ref*, the per-step graph of mpcq_mpc_run_ref_device).
+#define MPCQ_LANE_REF 1
+#include "mpcq_admm.h"
+
+extern "C" int mpcq_internal_admm_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const mpcq::RefArgs *ref,
+                                                 hipStream_t s)
+{
+    if (!ref || !ref->p) return -1;
+    return mpcq::launch_any<double>(*a, nc, mc, s, ref);
+}

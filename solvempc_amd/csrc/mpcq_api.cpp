@@ -134,7 +134,16 @@ struct mpcq_ctx {
     // variant flags (all_ineq, lower_free) may change; a replay needs the generation it captured
     unsigned long long gen = 1;
     struct { double *X, *U; double xref, noise; unsigned long long seed; long long first_qp; hipStream_t s;
-             unsigned long long gen; } gkey{};
+             unsigned long long gen; const double *sched; int sched_len; long long sched_stride; } gkey{};
+    // per-QP horizon references (mpcq_mpc_step_ref*, mpcq_mpc_run_ref_device): the reference of the call in
+    // progress (p == null: a scalar-xref call), read by launch_typed / launch_stream / launch_tile_stream;
+    // d_ref: the host form's staging buffer (ref_cap doubles); d_ordG: G = -A P^-1 Fr (m x n) of the
+    // hardest-first order's key (ordG_ok when it matches d_ordmap)
+    mpcq::RefArgs cur_ref{};
+    double *d_ref = nullptr;
+    size_t ref_cap = 0;
+    double *d_ordG = nullptr;
+    bool ordG_ok = false;
     // what the captured step leaves lazy (x, y; rho; status, iter; q, u) and its order flag: every replay
     // leaves the same, whatever a reader materialised in between
     struct { bool xy, rho, info, qu, ord; double xref; } glazy{};
@@ -539,7 +548,7 @@ int mpcq_destroy(mpcq_ctx *c)
                     c->d_Sbar, c->d_Ku, c->d_W0, c->d_X, c->d_U, c->d_img, c->d_list, c->d_counts,
                     c->d_itstate, c->d_Ad, c->d_Bd, c->d_step, c->d_flags, c->d_stamps, c->d_mimo,
                     c->d_it_acc, c->d_uns_acc, c->d_Xs, c->d_Us, c->d_ordmap, c->d_ord, c->d_pol_status,
-                    c->d_pol_nact, c->d_pol_res};
+                    c->d_pol_nact, c->d_pol_res, c->d_ref, c->d_ordG};
     if (c->gexec) (void)hipGraphExecDestroy(c->gexec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     for (void *p : ptrs)
@@ -845,6 +854,10 @@ static const char *env_kernel() { return test_hook("MPCQ_KERNEL"); }
 template <typename T>
 static int wave_launch(mpcq_ctx *c, const mpcq::AdmmArgs<T> &a, int grid, hipStream_t s)
 {
+    if (c->cur_ref.p && a.mpc)  // an MPC front end with per-QP references: the REF variant
+        return std::is_same<T, float>::value
+                   ? mpcq_internal_wave_ref_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, grid, &c->cur_ref, s)
+                   : mpcq_internal_wave_ref_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, grid, &c->cur_ref, s);
     return std::is_same<T, float>::value
                ? mpcq_internal_wave_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, grid, s)
                : mpcq_internal_wave_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, grid, s);
@@ -860,7 +873,9 @@ static int launch_phases(mpcq_ctx *c, mpcq::AdmmArgs<T> &a, hipStream_t s, bool 
     bool wave_tail = false;
     // an MPC step on the tile waves runs its batch hardest-first (mpcq_order.hip; test hook MPCQ_ORDER=0:
     // index order)
-    const bool ordered = a.mpc && a.X && a.U && c->ord_ok && !wave_only && test_hook("MPCQ_ORDER")[0] != '0';
+    // (a step with per-QP references: the key's G ref_b term needs the folded G, build_order_map)
+    const bool ordered = a.mpc && a.X && a.U && c->ord_ok && !wave_only && test_hook("MPCQ_ORDER")[0] != '0' &&
+                         (!c->cur_ref.p || c->ordG_ok);
     const int np = phase_stops(c->set, B, c->cus, stops, &wave_tail, ordered);
     c->ord_last = ordered;
     int *const ord_cnt = c->d_ord, *const ord_key = c->d_ord + mpcq::OrderBins::kBins, *const ord_list = ord_key + B;
@@ -868,8 +883,12 @@ static int launch_phases(mpcq_ctx *c, mpcq::AdmmArgs<T> &a, hipStream_t s, bool 
         // the counters are zero unless the last ordered sort's tile launch did not run (it clears them)
         if (!c->ord_clean && hipMemsetAsync(ord_cnt, 0, 4 * (size_t)mpcq::OrderBins::kBins, s) != hipSuccess) return -2;
         c->ord_clean = false;
-        if (mpcq_internal_order(B, c->nx, c->dims.m, a.X, a.U, c->d_ordmap, a.xref, ord_cnt, ord_key, ord_list,
-                                a.X_save, a.U_save, s) != 0)
+        if (c->cur_ref.p) {
+            if (mpcq_internal_order_ref(B, c->nx, c->dims.n, c->dims.m, a.X, a.U, c->d_ordmap, c->d_ordG, &c->cur_ref, ord_cnt,
+                                        ord_key, ord_list, a.X_save, a.U_save, s) != 0)
+                return -2;
+        } else if (mpcq_internal_order(B, c->nx, c->dims.m, a.X, a.U, c->d_ordmap, a.xref, ord_cnt, ord_key, ord_list,
+                                       a.X_save, a.U_save, s) != 0)
             return -2;
     }
     // (an ordered step's X, U copies are the order kernel's: its phase-0 tile launch skips them)
@@ -943,9 +962,14 @@ static int launch_phases(mpcq_ctx *c, mpcq::AdmmArgs<T> &a, hipStream_t s, bool 
             break;
         }
         // every phase launches the phase-0 grid: list segment s is served by the blocks b % kShards == s
-        rc = std::is_same<T, float>::value
-                 ? mpcq_internal_tile_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, s)
-                 : mpcq_internal_tile_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, s);
+        if (c->cur_ref.p && a.X)  // per-QP references: the REF variants (every phase re-forms q from X, U and ref)
+            rc = std::is_same<T, float>::value
+                     ? mpcq_internal_tile_ref_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, &c->cur_ref, s)
+                     : mpcq_internal_tile_ref_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, &c->cur_ref, s);
+        else
+            rc = std::is_same<T, float>::value
+                     ? mpcq_internal_tile_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, s)
+                     : mpcq_internal_tile_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, s);
         if (rc) return rc;
         c->count0_clean = a.zero_cnt0 != nullptr;
         if (a.ord_zero) c->ord_clean = true;
@@ -995,10 +1019,15 @@ static int launch_args(mpcq_ctx *c, mpcq::AdmmArgs<T> &a, hipStream_t s)
 {
     const PathChoice p = choose_path(c);
     a.paired = p.paired;
-    if (p.kind == MPCQ_PATH_LANE)
+    if (p.kind == MPCQ_PATH_LANE) {
+        if (c->cur_ref.p && a.mpc)  // an MPC front end with per-QP references: the REF variant
+            return std::is_same<T, float>::value
+                       ? mpcq_internal_admm_ref_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, &c->cur_ref, s)
+                       : mpcq_internal_admm_ref_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, &c->cur_ref, s);
         return std::is_same<T, float>::value
                    ? mpcq_internal_admm_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, s)
                    : mpcq_internal_admm_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, s);
+    }
     if (!c->tile) {  // per-plant batches: one QP per wave (operators in VGPRs)
         a.stop_iter = c->set.max_iter;
         return wave_launch<T>(c, a, c->dims.batch, s);
@@ -1014,7 +1043,9 @@ static int launch_typed(mpcq_ctx *c, hipStream_t s, bool mpc, const double *X, d
         a.mpc = 1; a.mpc_u = 1; a.nx = c->nx; a.X = X; a.U = U; a.xref = xref;
         if (c->set.polish) a.mpc_u = 0;  // (the applied move is the polished one: polish_kernel's U += x[0])
         a.Fx = c->d_Fx; a.Fu = c->d_Fu; a.Fr = c->d_Fr; a.Sbar = c->d_Sbar; a.Ku = c->d_Ku; a.W0 = c->d_W0;
-        const bool lazy = c->tile && choose_path(c).kind == MPCQ_PATH_TILE && c->d_Xs && c->d_Us;
+        // (a step with per-QP references writes q, u eagerly on every path: q must outlive the caller's
+        // reference buffer, and a saved window would need its own copy, buffer and front-end variant)
+        const bool lazy = c->tile && choose_path(c).kind == MPCQ_PATH_TILE && c->d_Xs && c->d_Us && !c->cur_ref.p;
         if (lazy) {  // phase 0 saves X, U (40 B/QP) instead of writing q, u (480 B/QP): materialize_qu
             a.X_save = c->d_Xs; a.U_save = c->d_Us;
         } else {
@@ -1450,7 +1481,7 @@ static int materialize_info(mpcq_ctx *c)
 static bool order_map_rows(int n, int m, int nx, const std::vector<double> &P, const std::vector<double> &A,
                            const std::vector<double> &Fx, const std::vector<double> &Fu, const std::vector<double> &Fr,
                            const std::vector<double> &Sb, const std::vector<double> &Ku, const std::vector<double> &W0,
-                           std::vector<double> &map)
+                           std::vector<double> &map, std::vector<double> *G = nullptr)
 {
     // Cholesky P = L L' (lower L in place, from P's upper triangle)
     std::vector<double> L((size_t)n * n, 0.0);
@@ -1502,6 +1533,31 @@ static bool order_map_rows(int n, int m, int nx, const std::vector<double> &P, c
         for (int k = 0; k < KS; k++)
             if (!std::isfinite(row[k])) return false;
     }
+    // per-QP references (mpcq_mpc_step_ref*): the xref column generalises to G = -A P^-1 Fr (m x n), so that
+    // v gains G ref_b; G left empty where a row is not finite (reference steps then run in index order)
+    if (G) {
+        std::vector<double> Y((size_t)n * n);  // P^-1 Fr, column by column
+        for (int r = 0; r < n; r++) {
+            for (int i = 0; i < n; i++) {  // L y = b
+                double v = Fr[(size_t)i * n + r];
+                for (int k = 0; k < i; k++) v -= L[(size_t)i * n + k] * Y[(size_t)k * n + r];
+                Y[(size_t)i * n + r] = v / L[(size_t)i * n + i];
+            }
+            for (int i = n - 1; i >= 0; i--) {  // L' z = y
+                double v = Y[(size_t)i * n + r];
+                for (int k = i + 1; k < n; k++) v -= L[(size_t)k * n + i] * Y[(size_t)k * n + r];
+                Y[(size_t)i * n + r] = v / L[(size_t)i * n + i];
+            }
+        }
+        G->assign((size_t)m * n, 0.0);
+        for (int j = 0; j < m && !G->empty(); j++)
+            for (int r = 0; r < n; r++) {
+                double s = 0.0;
+                for (int i = 0; i < n; i++) s += A[(size_t)j * n + i] * Y[(size_t)i * n + r];
+                if (!std::isfinite(s)) { G->clear(); break; }
+                (*G)[(size_t)j * n + r] = -s;
+            }
+    }
     return true;
 }
 
@@ -1541,9 +1597,16 @@ static int build_order_map(mpcq_ctx *c)
     HIPCHK(hipMemcpyAsync(Ku.data(), c->d_Ku, 8 * Ku.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(W0.data(), c->d_W0, 8 * W0.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    std::vector<double> map;
-    if (!order_map_rows(n, m, nx, P, A, Fx, Fu, Fr, Sb, Ku, W0, map)) return MPCQ_OK;
+    std::vector<double> map, G;
+    c->ordG_ok = false;
+    if (!order_map_rows(n, m, nx, P, A, Fx, Fu, Fr, Sb, Ku, W0, map, &G)) return MPCQ_OK;
     if (int rc = upload_order_map(c, map, s)) return rc;
+    if (!G.empty() && n <= 32) {  // (the order kernel's LDS rows of G: kOrderRefN columns)
+        if (!c->d_ordG && hipMalloc((void **)&c->d_ordG, 8 * (size_t)mpcq::OrderBins::kMaxRows * 32) != hipSuccess)
+            return fail(MPCQ_ERR_HIP, "hipMalloc failed (order map)");
+        if (int rc = h2d(c->d_ordG, G.data(), 8 * G.size(), s)) return rc;
+        c->ordG_ok = true;
+    }
     c->ord_ok = true;
     c->pord_ok = false;  // (the map is now this plant's)
     return MPCQ_OK;
@@ -1587,6 +1650,59 @@ int mpcq_mpc_step(mpcq_ctx *c, const double *X, double *U, double xref)
     const size_t B = c->dims.batch;
     if ((rc = h2d(c->d_X, X, 8 * B * c->nx, c->last)) || (rc = h2d(c->d_U, U, 8 * B, c->last))) return rc;
     if ((rc = launch_solve(c, c->last, true, c->d_X, c->d_U, xref))) return rc;
+    return d2h(c, U, c->d_U, 8 * B);
+}
+
+// The call in progress runs with per-QP references: launch_typed / launch_stream / launch_tile_stream read
+// c->cur_ref, which is the scalar xref again when the call returns.
+namespace {
+struct RefScope {
+    mpcq_ctx *c;
+    RefScope(mpcq_ctx *cc, const mpcq::RefArgs &r) : c(cc) { c->cur_ref = r; }
+    ~RefScope() { c->cur_ref = mpcq::RefArgs{}; }
+};
+}  // namespace
+
+int mpcq_mpc_step_ref_device(mpcq_ctx *c, const double *X, double *U, const double *ref, long long ref_stride,
+                             void *stream)
+{
+    int rc = check_ctx(c, kGeneric);
+    if (rc) return rc;
+    if (!c->mpc_ready) return fail(MPCQ_ERR_ORDER, "mpcq_mpc_set_operators has not been called");
+    if (!X || !U) return fail(MPCQ_ERR_ARG, "null X/U");
+    if (!ref) return fail(MPCQ_ERR_ARG, "null ref");
+    if (ref_stride != 0 && ref_stride < c->dims.n) return fail(MPCQ_ERR_ARG, "ref_stride must be 0 or >= n");
+    RefScope scope(c, mpcq::RefArgs{ref, ref_stride, 0, nullptr, c->dims.n});
+    return launch_solve(c, (hipStream_t)stream, true, X, U, 0.0);
+}
+
+int mpcq_mpc_step_ref(mpcq_ctx *c, const double *X, double *U, const double *ref, long long ref_stride)
+{
+    int rc = check_ctx(c, kGeneric);
+    if (rc) return rc;
+    if (!c->mpc_ready) return fail(MPCQ_ERR_ORDER, "mpcq_mpc_set_operators has not been called");
+    if (!X || !U) return fail(MPCQ_ERR_ARG, "null X/U");
+    if (!ref) return fail(MPCQ_ERR_ARG, "null ref");
+    const size_t B = c->dims.batch, n = c->dims.n;
+    if (ref_stride != 0 && ref_stride < (long long)n) return fail(MPCQ_ERR_ARG, "ref_stride must be 0 or >= n");
+    // the staged copy is packed: B rows of n (or the one shared row)
+    const size_t rows = ref_stride ? B : 1;
+    if (c->ref_cap < rows * n) {
+        if ((rc = materialize_qu(c))) return rc;
+        HIPCHK(hipStreamSynchronize(c->last));  // (no solve still reads the buffer about to be freed)
+        if (c->d_ref) { (void)hipFree(c->d_ref); c->d_ref = nullptr; c->ref_cap = 0; }
+        if (hipMalloc((void **)&c->d_ref, 8 * rows * n) != hipSuccess) return fail(MPCQ_ERR_HIP, "hipMalloc failed");
+        c->ref_cap = rows * n;
+    }
+    if (ref_stride == 0 || ref_stride == (long long)n) {
+        if ((rc = h2d(c->d_ref, ref, 8 * rows * n, c->last))) return rc;
+    } else {
+        HIPCHK(hipMemcpy2DAsync(c->d_ref, 8 * n, ref, 8 * (size_t)ref_stride, 8 * n, rows, hipMemcpyHostToDevice, c->last));
+        HIPCHK(hipStreamSynchronize(c->last));
+    }
+    if ((rc = h2d(c->d_X, X, 8 * B * c->nx, c->last)) || (rc = h2d(c->d_U, U, 8 * B, c->last))) return rc;
+    RefScope scope(c, mpcq::RefArgs{c->d_ref, ref_stride ? (long long)n : 0, 0, nullptr, (int)n});
+    if ((rc = launch_solve(c, c->last, true, c->d_X, c->d_U, 0.0))) return rc;
     return d2h(c, U, c->d_U, 8 * B);
 }
 
@@ -1650,8 +1766,13 @@ static int launch_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, doubl
     a.mpc = 1; a.mpc_u = 1; a.nx = c->nx; a.X = X; a.U = U; a.xref = xref;
     a.Fx = c->d_Fx; a.Fu = c->d_Fu; a.Fr = c->d_Fr; a.Sbar = c->d_Sbar; a.Ku = c->d_Ku; a.W0 = c->d_W0;
     a.q_out = c->d_q; a.u_out = c->d_u;
+    // (a reference schedule, c->cur_ref: the REF variant slides the window with the step)
     a.stop_iter = c->set.max_iter;
     c->qu_lazy = false;
+    if (c->cur_ref.p)
+        return std::is_same<T, float>::value
+                   ? mpcq_internal_stream_ref_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, &sa, &c->cur_ref, s)
+                   : mpcq_internal_stream_ref_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, &sa, &c->cur_ref, s);
     return std::is_same<T, float>::value
                ? mpcq_internal_stream_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, &sa, s)
                : mpcq_internal_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, &sa, s);
@@ -1690,6 +1811,10 @@ static int launch_tile_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, 
     a.mpc = 1; a.mpc_u = 1; a.nx = c->nx; a.X = X; a.U = U; a.xref = xref;
     a.Fx = c->d_Fx; a.Fu = c->d_Fu; a.Fr = c->d_Fr; a.Sbar = c->d_Sbar; a.Ku = c->d_Ku; a.W0 = c->d_W0;
     a.X_save = c->d_Xs; a.U_save = c->d_Us;  // the last step's X, U: its q, u on demand (materialize_qu)
+    if (c->cur_ref.p) {  // a reference schedule: the last step's q, u themselves (its window is not kept)
+        a.X_save = a.U_save = nullptr;
+        a.q_out = c->d_q; a.u_out = c->d_u;
+    }
     a.paired = 1;
     a.img = (const T *)c->d_img;
     a.stop_iter = INT_MAX;
@@ -1706,9 +1831,13 @@ static int launch_tile_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, 
             return -2;
         a.stamps = c->d_stamps;
     }
-    const int rc = std::is_same<T, float>::value
+    const int rc =
+        c->cur_ref.p ? (std::is_same<T, float>::value
+                       ? mpcq_internal_tile_ref_stream_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, &c->cur_ref, s)
+                       : mpcq_internal_tile_ref_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, &c->cur_ref, s))
+                : (std::is_same<T, float>::value
                        ? mpcq_internal_tile_stream_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, s)
-                       : mpcq_internal_tile_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, s);
+                       : mpcq_internal_tile_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, s));
     if (rc == 0 && stp && *stp) {
         std::vector<long long> h(8 * swaves);
         if (hipMemcpyAsync(h.data(), c->d_stamps, 8 * h.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -1724,24 +1853,35 @@ static int launch_tile_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, 
         c->d_stamps = nullptr;
     }
     if (rc == 0) {
-        c->qu_lazy = true;
+        c->qu_lazy = !c->cur_ref.p;
         c->lazy_xref = xref;
     }
     return rc;
 }
 extern "C" {
 
-int mpcq_mpc_run_device(mpcq_ctx *c, double *X, double *U, double xref, int steps, unsigned long long seed,
-                        long long first_qp, long long first_step, double noise_std, void *stream)
+// mpcq_mpc_run_device (sched == null: the scalar xref) and mpcq_mpc_run_ref_device (the schedule sched_dev,
+// sched_len, sched_stride in place of xref).
+static int mpc_run(mpcq_ctx *c, const char *fn, double *X, double *U, double xref, const double *sched, int sched_len,
+                   long long sched_stride, int steps, unsigned long long seed, long long first_qp, long long first_step,
+                   double noise_std, void *stream)
 {
     int rc = check_ctx(c, kGeneric);
     if (rc) return rc;
-    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal("mpcq_mpc_run_device"));
+    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal(fn));
     if (!c->mpc_ready || !c->plant_nx) return fail(MPCQ_ERR_ORDER, "mpc operators / plant not set");
     if (c->plant_nx != c->nx) return fail(MPCQ_ERR_ARG, "plant nx differs from the operators' nx");
     if (!X || !U || steps < 0) return fail(MPCQ_ERR_ARG, "null X/U or steps < 0");
     if (!stream) return fail(MPCQ_ERR_ARG, "graph capture needs a non-NULL stream");
     hipStream_t s = (hipStream_t)stream;
+    // the one-launch kernels slide the window from first_step themselves; the per-step launches (eager first
+    // step, captured graph) take the step from the device counter, as the captured plant simulation does
+    mpcq::RefArgs ref_launch{}, ref_graph{};
+    if (sched) {
+        ref_launch = mpcq::RefArgs{sched, sched_stride, first_step, nullptr, sched_len};
+        ref_graph = mpcq::RefArgs{sched, sched_stride, 0, c->d_step, sched_len};
+    }
+    RefScope scope(c, ref_launch);
     HIPCHK(hipMemsetAsync(c->d_it_acc, 0, 4 * (size_t)c->dims.batch, s));
     HIPCHK(hipMemsetAsync(c->d_uns_acc, 0, 4 * (size_t)c->dims.batch, s));
     if (steps == 0) return MPCQ_OK;
@@ -1794,6 +1934,7 @@ int mpcq_mpc_run_device(mpcq_ctx *c, double *X, double *U, double xref, int step
     }
     int done = 0;
     c->stream_path = MPCQ_STREAM_GRAPH;
+    c->cur_ref = ref_graph;
     if (c->fresh) {  // a reset is a one-off (x = z = y = 0): run that step eagerly, capture the rest
         if ((rc = launch_solve(c, s, true, X, U, xref))) return rc;
         if (mpcq_internal_simulate(c->dims.batch, c->nx, c->dims.n_plants == 1, c->d_Ad, c->d_Bd, X, U, seed,
@@ -1805,7 +1946,8 @@ int mpcq_mpc_run_device(mpcq_ctx *c, double *X, double *U, double xref, int step
     }
     const bool same = c->gexec && c->gkey.X == X && c->gkey.U == U && c->gkey.xref == xref &&
                       c->gkey.noise == noise_std && c->gkey.seed == seed && c->gkey.first_qp == first_qp &&
-                      c->gkey.s == s && c->gkey.gen == c->gen;
+                      c->gkey.s == s && c->gkey.gen == c->gen && c->gkey.sched == sched &&
+                      (!sched || (c->gkey.sched_len == sched_len && c->gkey.sched_stride == sched_stride));
     if (!same && done < steps) {
         if (c->gexec) { (void)hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
         if (c->graph) { (void)hipGraphDestroy(c->graph); c->graph = nullptr; }
@@ -1828,7 +1970,7 @@ int mpcq_mpc_run_device(mpcq_ctx *c, double *X, double *U, double xref, int step
             c->gexec = nullptr;
             return fail(MPCQ_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei));
         }
-        c->gkey = {X, U, xref, noise_std, seed, first_qp, s, c->gen};
+        c->gkey = {X, U, xref, noise_std, seed, first_qp, s, c->gen, sched, sched_len, sched_stride};
         c->glazy = {c->xy_lazy, c->rho_lazy, c->info_lazy, c->qu_lazy, c->ord_last, c->lazy_xref};
     }
     for (int k = done; k < steps; k++) {
@@ -1849,6 +1991,26 @@ int mpcq_mpc_run_device(mpcq_ctx *c, double *X, double *U, double xref, int step
     }
     c->last = s;
     return MPCQ_OK;
+}
+
+int mpcq_mpc_run_device(mpcq_ctx *c, double *X, double *U, double xref, int steps, unsigned long long seed,
+                        long long first_qp, long long first_step, double noise_std, void *stream)
+{
+    return mpc_run(c, "mpcq_mpc_run_device", X, U, xref, nullptr, 0, 0, steps, seed, first_qp, first_step, noise_std,
+                   stream);
+}
+
+int mpcq_mpc_run_ref_device(mpcq_ctx *c, double *X, double *U, const double *sched, int sched_len,
+                            long long sched_stride, int steps, unsigned long long seed, long long first_qp,
+                            long long first_step, double noise_std, void *stream)
+{
+    if (!c) return fail(MPCQ_ERR_ARG, "null context");
+    if (!sched) return fail(MPCQ_ERR_ARG, "null schedule");
+    if (sched_len < 1) return fail(MPCQ_ERR_ARG, "sched_len must be >= 1");
+    if (sched_stride != 0 && sched_stride < sched_len) return fail(MPCQ_ERR_ARG, "sched_stride must be 0 or >= sched_len");
+    if (first_step < 0) return fail(MPCQ_ERR_ARG, "first_step must be >= 0");
+    return mpc_run(c, "mpcq_mpc_run_ref_device", X, U, 0.0, sched, sched_len, sched_stride, steps, seed, first_qp,
+                   first_step, noise_std, stream);
 }
 
 int mpcq_condense(int device, int n_plants, int nx, int N, int s_rows, const double *Ad, const double *Bd,

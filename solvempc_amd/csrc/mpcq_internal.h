@@ -173,6 +173,29 @@ struct StreamArgs {
                                   // wave per SIMD, the whole register file, no spills; 2 otherwise)
 };
 
+// Per-QP horizon reference of the MPC front end (mpcq_mpc_step_ref*, mpcq_mpc_run_ref_device; read by the
+// REF kernel variants only): the control step with absolute index s uses, for QP b,
+//     ref_b[j] = p[b stride + min(s + j, len - 1)],   j = 0 .. n - 1
+// (stride 0: one row shared by the batch).  One controllerStep: len = n, s = 0 (the row is the window).
+// A stream: s = step + k for the launch's k-th control step, the step taken from *step_p where non-null
+// (the captured per-step graph: the context's device step counter).  p == null: the scalar xref.
+// It is a kernel argument of its own, next to AdmmArgs, so that the scalar kernels' arguments (and code)
+// are what they were.
+struct RefArgs {
+    const double *p;
+    long long stride, step;
+    const long long *step_p;
+    int len;
+    // the window's first schedule entry at the launch's k-th control step, and element j of QP row `row`
+    __device__ __forceinline__ long long first(int k) const { return (step_p ? *step_p : step) + k; }
+    __device__ __forceinline__ const double *row(long long b) const { return p + b * stride; }
+    __device__ __forceinline__ double at(const double *row, long long s0, int j) const
+    {
+        const long long i = s0 + j;
+        return row[i < len ? i : len - 1];
+    }
+};
+
 template <typename T>
 struct AdmmArgs {
     int batch, n, m;
@@ -434,6 +457,13 @@ int mpcq_internal_condense_launch(const mpcq::CondenseArgs *a, hipStream_t s);
 size_t mpcq_internal_condense_scratch(int nx, int N);
 int mpcq_internal_admm_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, hipStream_t s);
 int mpcq_internal_admm_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, hipStream_t s);
+// The REF variants of the launchers (mpcq_*_ref_*.hip: the same kernels compiled with a per-QP horizon
+// reference, RefArgs, as a trailing kernel argument; the lane kernel here, the wave, stream and tile kernels
+// below).  Same return codes; -1 also for a null reference.
+int mpcq_internal_admm_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const mpcq::RefArgs *ref,
+                                      hipStream_t s);
+int mpcq_internal_admm_ref_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const mpcq::RefArgs *ref,
+                                      hipStream_t s);
 int mpcq_internal_warm_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const double *x, const double *y,
                            hipStream_t s);
 int mpcq_internal_warm_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const double *x, const double *y,
@@ -449,16 +479,34 @@ int mpcq_internal_tile_publish_f32(const mpcq::AdmmArgs<float> *a, int KN, int K
 // control steps).  0 launched, -1 not the paired condensed-MPC shape.
 int mpcq_internal_tile_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, hipStream_t s);
 int mpcq_internal_tile_stream_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, hipStream_t s);
+// The same launches with a per-QP horizon reference (the tile kernel's REF variants, mpcq_tile_ref_f64.hip /
+// mpcq_tile_ref_f32.hip); same return codes.
+int mpcq_internal_tile_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, const mpcq::RefArgs *ref,
+                                      hipStream_t s);
+int mpcq_internal_tile_ref_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, const mpcq::RefArgs *ref,
+                                      hipStream_t s);
+int mpcq_internal_tile_ref_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, const mpcq::RefArgs *ref,
+                                             hipStream_t s);
+int mpcq_internal_tile_ref_stream_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, const mpcq::RefArgs *ref,
+                                             hipStream_t s);
 // One-QP-per-wave path (mpcq_wave.h): grid blocks of 64 threads stride over the (listed) QPs;
 // -1 = n > 32 or m > 64 (not compiled).
 int mpcq_internal_wave_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, int grid, hipStream_t s);
 int mpcq_internal_wave_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, int grid, hipStream_t s);
+int mpcq_internal_wave_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, int grid, const mpcq::RefArgs *ref,
+                                      hipStream_t s);
+int mpcq_internal_wave_ref_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, int grid, const mpcq::RefArgs *ref,
+                                      hipStream_t s);
 // The receding-horizon stream in one launch (mpcq_wave.h stream_wave_kernel): every wave owns one QP
 // for all `steps` control steps (solve, U += x0, plant update).  0 launched, -1 no compiled capacity.
 int mpcq_internal_stream_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const mpcq::StreamArgs *sa,
                                     hipStream_t s);
 int mpcq_internal_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const mpcq::StreamArgs *sa,
                                     hipStream_t s);
+int mpcq_internal_stream_ref_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const mpcq::StreamArgs *sa,
+                                        const mpcq::RefArgs *ref, hipStream_t s);
+int mpcq_internal_stream_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const mpcq::StreamArgs *sa,
+                                        const mpcq::RefArgs *ref, hipStream_t s);
 // Plant update of the receding-horizon stream (mpcq_stream.hip); step from *step_p when non-null.
 int mpcq_internal_simulate(int batch, int nx, int shared, const double *Ad, const double *Bd, double *X,
                            const double *U, unsigned long long seed, long long first_qp, const long long *step_p,
@@ -473,6 +521,11 @@ int mpcq_internal_set_step(long long *step, long long v, hipStream_t s);
 // (or null): copies of X, U for the step's q, u on demand.
 int mpcq_internal_order(int batch, int nx, int m, const double *X, const double *U, const double *kmap, double xref,
                         int *cnt, int *key, int *list, double *Xs, double *Us, hipStream_t s);
+// The same order for a step with per-QP references: the key gains G ref_b, G = -A P^-1 Fr (gmap: m x n,
+// row-major, folded by the host next to kmap; the map's xref column is not used).
+int mpcq_internal_order_ref(int batch, int nx, int n, int m, const double *X, const double *U, const double *kmap,
+                            const double *gmap, const mpcq::RefArgs *ref, int *cnt, int *key, int *list, double *Xs,
+                            double *Us, hipStream_t s);
 // status[list[i]], iter[list[i]] = slot[2 i], slot[2 i + 1] (an ordered launch's AdmmArgs::info_slot)
 int mpcq_internal_order_info(int batch, const int *list, const int *slot, int *status, int *iter, hipStream_t s);
 // MIMO condensed MPC (mpcq_mimo.hip): per-plant condensing + Ruiz + P^, then the per-QP solve

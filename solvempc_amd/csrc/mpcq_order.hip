@@ -32,15 +32,27 @@ namespace mpcq {
 // of different rows overlap), 256 QPs per 1,024-thread workgroup: the key's latency is spread over 16 waves
 // per workgroup, and a workgroup's global atomics (one per non-empty bin) cover 256 QPs.
 constexpr int kOrderThreads = 1024, kOrderQPW = kOrderThreads / 4;
+// REF (mpcq_mpc_step_ref*): the QP's own horizon reference ref_b in place of xref 1; the key gains
+// (G ref_b)_j, G = -A P^-1 Fr (gmap, m x n with n <= kOrderRefN, in LDS next to the map), so that it stays
+// the key of the QP's actual q.  The scalar kernel (REF false) is the code it was.
+constexpr int kOrderRefN = 32;
+template <bool REF>
 __global__ __launch_bounds__(kOrderThreads) void order_key_kernel(int batch, int nx, int m, const double *__restrict__ X,
                                                                   const double *__restrict__ U,
                                                                   const double *__restrict__ kmap, double xref,
                                                                   int *__restrict__ cnt, int *__restrict__ key,
-                                                                  double *__restrict__ Xs, double *__restrict__ Us)
+                                                                  double *__restrict__ Xs, double *__restrict__ Us,
+                                                                  int n, const double *__restrict__ gmap, RefArgs ref)
 {
     constexpr int KB = OrderBins::kBins, KS = OrderBins::kStride, RPT = OrderBins::kMaxRows / 4;
     __shared__ double k[OrderBins::kMaxRows * KS];
+    __shared__ double gk[REF ? OrderBins::kMaxRows * kOrderRefN : 1];  // G, rows padded to kOrderRefN
     __shared__ int h[KB], base[KB];
+    if constexpr (REF)
+        for (int i = threadIdx.x; i < m * kOrderRefN; i += blockDim.x) {
+            const int j = i / kOrderRefN, t = i % kOrderRefN;
+            gk[i] = t < n ? gmap[(size_t)j * n + t] : 0.0;
+        }
     for (int i = threadIdx.x; i < m * KS; i += blockDim.x) k[i] = i % KS == 9 ? __builtin_fma(kmap[i + 1], xref, kmap[i]) : kmap[i];
     for (int i = threadIdx.x; i < KB; i += blockDim.x) h[i] = 0;
     const int part = threadIdx.x & 3;
@@ -64,17 +76,46 @@ __global__ __launch_bounds__(kOrderThreads) void order_key_kernel(int batch, int
     __syncthreads();
     // rows part, part + 4, ... (interleaved: the four threads of a QP read different rows of one LDS line)
     double v = -__builtin_inf();
+    if constexpr (REF) {
+        // (xref is 0 here: r[9] = -W0.)  The G ref_b term row by row over the window, one load of ref_b[t]
+        // serving the thread's RPT rows
+        double sr[RPT];
 #pragma unroll
-    for (int q = 0; q < RPT; q++) {
-        const int j = 4 * q + part;
-        if (j < m) {
-            const double *r = k + KS * j;
-            double s = r[9];  // (-A P^-1 Fr 1) xref - W0, formed above
+        for (int q = 0; q < RPT; q++) {
+            const int j = 4 * q + part;
+            const double *r = k + KS * (j < m ? j : 0);
+            double s = r[9];
 #pragma unroll
             for (int t = 0; t < 8; t++)
                 if (t < nx) s = __builtin_fma(r[t], x[t], s);
-            s = __builtin_fma(r[8], u, s);
-            v = __builtin_fmax(v, s);
+            sr[q] = __builtin_fma(r[8], u, s);
+        }
+        const double *rrow = ref.row(bb);
+        const long long s0 = ref.first(0);
+        for (int t = 0; t < n; t++) {
+            const double rt = ref.at(rrow, s0, t);
+#pragma unroll
+            for (int q = 0; q < RPT; q++) {
+                const int j = 4 * q + part;
+                sr[q] = __builtin_fma(gk[kOrderRefN * (j < m ? j : 0) + t], rt, sr[q]);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < RPT; q++)
+            if (4 * q + part < m) v = __builtin_fmax(v, sr[q]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < RPT; q++) {
+            const int j = 4 * q + part;
+            if (j < m) {
+                const double *r = k + KS * j;
+                double s = r[9];  // (-A P^-1 Fr 1) xref - W0, formed above
+#pragma unroll
+                for (int t = 0; t < 8; t++)
+                    if (t < nx) s = __builtin_fma(r[t], x[t], s);
+                s = __builtin_fma(r[8], u, s);
+                v = __builtin_fmax(v, s);
+            }
         }
     }
     v = __builtin_fmax(v, __shfl_xor(v, 1));  // the QP's four quarters (lanes 4 i .. 4 i + 3)
@@ -162,8 +203,25 @@ extern "C" int mpcq_internal_order(int batch, int nx, int m, const double *X, co
         m > mpcq::OrderBins::kMaxRows)
         return -1;
     const int blocks = (batch + 255) / 256;
-    hipLaunchKernelGGL(mpcq::order_key_kernel, dim3((batch + mpcq::kOrderQPW - 1) / mpcq::kOrderQPW),
-                       dim3(mpcq::kOrderThreads), 0, s, batch, nx, m, X, U, kmap, xref, cnt, key, Xs, Us);
+    hipLaunchKernelGGL(mpcq::order_key_kernel<false>, dim3((batch + mpcq::kOrderQPW - 1) / mpcq::kOrderQPW),
+                       dim3(mpcq::kOrderThreads), 0, s, batch, nx, m, X, U, kmap, xref, cnt, key, Xs, Us, 0, nullptr,
+                       mpcq::RefArgs{});
+    if (hipGetLastError() != hipSuccess) return -2;
+    hipLaunchKernelGGL(mpcq::order_scatter_kernel, dim3(blocks), dim3(256), 0, s, batch, (const int *)cnt,
+                       (const int *)key, list);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int mpcq_internal_order_ref(int batch, int nx, int n, int m, const double *X, const double *U,
+                                       const double *kmap, const double *gmap, const mpcq::RefArgs *ref, int *cnt,
+                                       int *key, int *list, double *Xs, double *Us, hipStream_t s)
+{
+    if (batch <= 0 || batch >= (1 << mpcq::OrderBins::kRankBits) || nx <= 0 || nx > 8 || m <= 0 ||
+        m > mpcq::OrderBins::kMaxRows || n <= 0 || n > mpcq::kOrderRefN || !ref || !ref->p || !gmap)
+        return -1;
+    const int blocks = (batch + 255) / 256;
+    hipLaunchKernelGGL(mpcq::order_key_kernel<true>, dim3((batch + mpcq::kOrderQPW - 1) / mpcq::kOrderQPW),
+                       dim3(mpcq::kOrderThreads), 0, s, batch, nx, m, X, U, kmap, 0.0, cnt, key, Xs, Us, n, gmap, *ref);
     if (hipGetLastError() != hipSuccess) return -2;
     hipLaunchKernelGGL(mpcq::order_scatter_kernel, dim3(blocks), dim3(256), 0, s, batch, (const int *)cnt,
                        (const int *)key, list);

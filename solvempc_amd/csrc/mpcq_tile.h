@@ -469,10 +469,34 @@ __device__ __forceinline__ void reg_mv(const T (&m1)[kRegMvTiles<T, REM, NTO>][K
 // fp64 images); the last a.mix_r iterations before every info iteration (check, adapt, stop) run in fp64,
 // which damps the fp32 stretch's rounding below the north-star tolerance before the termination test,
 // adapt_rho and the solution read the state (tools/precision_sim.py).
+// REF (a translation unit that defines MPCQ_TILE_REF before this header: mpcq_tile_ref_*.hip; mpcq_mpc_step_ref*,
+// mpcq_mpc_run_ref_device): the same kernel text compiled as admm_tile_ref_kernel, whose front end reads every
+// QP's own horizon reference (RefArgs, a second kernel argument) in place of xref 1: Fr itself goes to LDS
+// (fp64, 4 KN x 4 KN) instead of its row sums, and a column's prologue (a stream column's every refill: the
+// window slides with its step) loads its n-vector and forms (Fr ref)_v in the scalar kernel's order and
+// expression form, so that a uniform reference reproduces it bit for bit.  The split is per translation unit
+// and not a template parameter or a shared body function so that admm_tile_kernel's instantiations keep
+// their names and their code: a wrapper around a shared body moved the register allocation of the scalar
+// stream kernel (2 % slower).
+#ifdef MPCQ_TILE_REF
+#define MPCQ_TILE_KERNEL admm_tile_ref_kernel
+#define MPCQ_TILE_REF_PARAM , RefArgs ref
+#define MPCQ_TILE_REF_ARG(r) , *(r)
+#else
+#define MPCQ_TILE_KERNEL admm_tile_kernel
+#define MPCQ_TILE_REF_PARAM
+#define MPCQ_TILE_REF_ARG(r)
+#endif
 template <typename T, int KN, int KM, bool ALL_INEQ, bool LFREE, int G, int OCC, bool PAIRED = false, int WPB = 4,
           bool STREAM = false, bool MIX = false>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void admm_tile_kernel(AdmmArgs<T> a)
+__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void MPCQ_TILE_KERNEL(AdmmArgs<T> a MPCQ_TILE_REF_PARAM)
 {
+#ifdef MPCQ_TILE_REF
+    constexpr bool REF = true;
+#else
+    constexpr bool REF = false;
+    const RefArgs ref{};  // (never read: every use is under `if constexpr (REF)`)
+#endif
     MPCQ_TSTAMP(0, (long long)__builtin_amdgcn_s_memtime());
     MPCQ_TSTAMP(6, (long long)__builtin_amdgcn_s_memrealtime());
     static_assert(!PAIRED || (KM == 2 * KN && ALL_INEQ && LFREE), "paired loop: m = 2n, inequality rows, l free");
@@ -548,6 +572,9 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
                   FE_W0 = 10 * NCP + 9 * MCP, FE_E = 10 * NCP + 10 * MCP, FE_D = 10 * NCP + 11 * MCP,
                   FE_TOT = 11 * NCP + 11 * MCP;
     __shared__ double fe[FE_TOT];
+    // REF: Fr itself, rows and columns padded (zeros) to the 4 KN elements a column's registers hold
+    constexpr int FRS = 4 * KN;
+    __shared__ double fe_fr[REF ? FRS * FRS : 1];
     // (an MPC step: every phase builds q, u from X, U; phase 0 also publishes them or saves X, U)
     const bool fe_on = a.X != nullptr;
     {
@@ -568,6 +595,12 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
                 fe[FE_KU + i] = i < m ? a.Ku[i] : 0.0;
                 fe[FE_W0 + i] = i < m ? a.W0[i] : 0.0;
             }
+            if constexpr (REF) {
+                for (int i = threadIdx.x; i < FRS * FRS; i += NTH) {
+                    const int v = i / FRS, t = i % FRS;
+                    fe_fr[i] = (v < n && t < n) ? a.Fr[(size_t)v * n + t] : 0.0;
+                }
+            } else
             if (threadIdx.x < n) {  // Fr ref, ref = xref 1 (updateRef :378-380): row sums in order t = 0..n-1
                 const int v = threadIdx.x;
                 double fr[NCP];
@@ -681,6 +714,14 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
                     pst[8] = Uv;
                 }
             }
+            // REF: the column's horizon reference, ref_b[t] (a stream column: the window of the step it starts)
+            double rf[REF ? FRS : 1];
+            if constexpr (REF) {
+                const double *rrow = ref.row(b);
+                const long long r0 = ref.first(refill ? kst[gi] : 0);
+#pragma unroll
+                for (int t = 0; t < FRS; t++) rf[t] = ref.at(rrow, r0, t < n ? t : 0);
+            }
 #pragma unroll
             for (int s = 0; s < KN; s++) {
                 const int v = 4 * s + g;  // < NCP: padded rows of fe are zero
@@ -689,7 +730,15 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
                 for (int t = 0; t < 8; t++)
                     if (t < nx) s0 += fe[FE_FX + 8 * v + t] * Xv[t];
                 const double s1 = fe[FE_FU + v] * Uv;
-                qk[s] = s0 + s1 + fe[FE_FR + v];
+                if constexpr (REF) {  // (Fr ref_b)_v in the order and form of the scalar kernel's row sums
+                    double s2 = 0.0;
+#pragma unroll
+                    for (int t = 0; t < FRS; t++)
+                        if (t < n) s2 += fe_fr[FRS * v + t] * rf[t];
+                    qk[s] = s0 + s1 + s2;
+                } else {
+                    qk[s] = s0 + s1 + fe[FE_FR + v];
+                }
                 if (mpc_fe && a.q_out && pub && v < n) a.q_out[(size_t)b * n + v] = qk[s];
             }
             if (mpc_fe && a.X_save && pub) {  // the step's X, U: q, u on demand (materialize_qu)
@@ -1998,21 +2047,23 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
 
 // Launch one tile-kernel variant: one workgroup per 64 G QPs of the phase's grid.
 // lds_pad: dynamic LDS bytes on top of the kernel's static allocation (0, or enough that fewer
-// workgroups fit a CU: the occupancy A/B below)
+// workgroups fit a CU: the occupancy A/B below).  ref: the REF translation units' second kernel argument
+// (MPCQ_TILE_REF_ARG: nothing in the scalar ones).  The launchers that name MPCQ_TILE_KERNEL are static: a
+// scalar and a REF translation unit each keep their own (one definition per unit, not one per program).
 template <typename T, int KN, int KM, bool AI, bool LF, int G, int OCC, bool PAIRED = false, int WPB = 4, bool MIX = false>
-int tile_launch_variant(const AdmmArgs<T> &a, hipStream_t s, unsigned lds_pad = 0)
+static int tile_launch_variant(const AdmmArgs<T> &a, hipStream_t s, unsigned lds_pad = 0, const RefArgs *ref = nullptr)
 {
     constexpr int QPW = 16 * G * WPB;
     const int blocks = (a.batch + QPW - 1) / QPW;
-    hipLaunchKernelGGL((admm_tile_kernel<T, KN, KM, AI, LF, G, OCC, PAIRED, WPB, false, MIX>), dim3(blocks), dim3(64 * WPB),
-                       lds_pad, s, a);
+    hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, AI, LF, G, OCC, PAIRED, WPB, false, MIX>), dim3(blocks), dim3(64 * WPB),
+                       lds_pad, s, a MPCQ_TILE_REF_ARG(ref));
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // The receding-horizon stream in one launch (AdmmArgs::sim): the paired condensed-MPC shape only
 // (-1 otherwise: the caller replays per-step launches).
 template <typename T, int KN, int KM>
-int tile_stream_launch(const AdmmArgs<T> &a, hipStream_t s)
+static int tile_stream_launch(const AdmmArgs<T> &a, hipStream_t s, const RefArgs *ref = nullptr)
 {
     if constexpr (KM == 2 * KN) {
         if (a.paired && a.all_ineq && a.lower_free) {
@@ -2025,16 +2076,16 @@ int tile_stream_launch(const AdmmArgs<T> &a, hipStream_t s)
             if constexpr (std::is_same<T, double>::value) {
                 if (a.mix_r > 0) {  // MPCQ_F64_MIXED: each step's plain iterations before the last mix_r in fp32
                     if (a.sim.occ == 1)
-                        hipLaunchKernelGGL((admm_tile_kernel<T, KN, KM, true, true, 1, 1, true, WPB, true, true>), grid, block, 0, s, a);
+                        hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 1, true, WPB, true, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref));
                     else
-                        hipLaunchKernelGGL((admm_tile_kernel<T, KN, KM, true, true, 1, 2, true, WPB, true, true>), grid, block, 0, s, a);
+                        hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 2, true, WPB, true, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref));
                     return hipGetLastError() == hipSuccess ? 0 : -2;
                 }
             }
             if (a.sim.occ == 1)
-                hipLaunchKernelGGL((admm_tile_kernel<T, KN, KM, true, true, 1, 1, true, WPB, true>), grid, block, 0, s, a);
+                hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 1, true, WPB, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref));
             else
-                hipLaunchKernelGGL((admm_tile_kernel<T, KN, KM, true, true, 1, 2, true, WPB, true>), grid, block, 0, s, a);
+                hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 2, true, WPB, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref));
             return hipGetLastError() == hipSuccess ? 0 : -2;
         }
     }
@@ -2044,24 +2095,24 @@ int tile_stream_launch(const AdmmArgs<T> &a, hipStream_t s)
 // One variant per shape and type (measured A/B): f32 runs one 16-QP group per
 // wave at 3 waves/SIMD, f64 at 2 (2 groups per wave, 4 waves/SIMD and 8-wave workgroups were slower).
 template <typename T, int KN, int KM>
-int tile_launch(const AdmmArgs<T> &a, hipStream_t s)
+static int tile_launch(const AdmmArgs<T> &a, hipStream_t s, const RefArgs *ref = nullptr)
 {
     constexpr int OCC = sizeof(T) == 8 ? 2 : 3;
     if constexpr (KM == 2 * KN) {
         if (a.paired && a.all_ineq && a.lower_free) {  // the condensed-MPC shape: paired, VGPR-resident loop
             if constexpr (std::is_same<T, double>::value) {
-                if (a.mix_r > 0) return tile_launch_variant<T, KN, KM, true, true, 1, OCC, true, 4, true>(a, s);
+                if (a.mix_r > 0) return tile_launch_variant<T, KN, KM, true, true, 1, OCC, true, 4, true>(a, s, 0, ref);
             } else {
                 // f32 at 2 waves/SIMD (AdmmArgs::tile_occ): a batch of 2 k rounds of 2,048 wave slots runs
                 // without the lone-wave last round 3 waves/SIMD leave (4,096 waves on 3,072 slots); the
                 // registers allow 3, so dynamic LDS holds a CU to 2 workgroups (> 160 KiB / 3 each)
-                if (a.tile_occ == 2) return tile_launch_variant<T, KN, KM, true, true, 1, OCC, true>(a, s, 16 * 1024);
+                if (a.tile_occ == 2) return tile_launch_variant<T, KN, KM, true, true, 1, OCC, true>(a, s, 16 * 1024, ref);
             }
-            return tile_launch_variant<T, KN, KM, true, true, 1, OCC, true>(a, s);
+            return tile_launch_variant<T, KN, KM, true, true, 1, OCC, true>(a, s, 0, ref);
         }
     }
-    if (a.all_ineq && a.lower_free) return tile_launch_variant<T, KN, KM, true, true, 1, OCC>(a, s);
-    return tile_launch_variant<T, KN, KM, false, false, 1, 2>(a, s);
+    if (a.all_ineq && a.lower_free) return tile_launch_variant<T, KN, KM, true, true, 1, OCC>(a, s, 0, ref);
+    return tile_launch_variant<T, KN, KM, false, false, 1, 2>(a, s, 0, ref);
 }
 
 // Lazily published solution of a tile solve (osqp store_solution, read by getSolution :105 only when a
@@ -2122,9 +2173,9 @@ int tile_publish(const AdmmArgs<T> &a, bool paired, hipStream_t s)
 #define MPCQ_TILE_SHAPES(X) X(1, 1) X(2, 3) X(4, 8) X(5, 10)
 
 template <typename T>
-int tile_launch_any(const AdmmArgs<T> &a, int KN, int KM, hipStream_t s)
+static int tile_launch_any(const AdmmArgs<T> &a, int KN, int KM, hipStream_t s, const RefArgs *ref = nullptr)
 {
-#define MPCQ_TRY(KN_, KM_) if (KN == KN_ && KM == KM_) return tile_launch<T, KN_, KM_>(a, s);
+#define MPCQ_TRY(KN_, KM_) if (KN == KN_ && KM == KM_) return tile_launch<T, KN_, KM_>(a, s, ref);
     MPCQ_TILE_SHAPES(MPCQ_TRY)
 #undef MPCQ_TRY
     return -1;
@@ -2140,9 +2191,9 @@ int tile_publish_any(const AdmmArgs<T> &a, int KN, int KM, bool paired, hipStrea
 }
 
 template <typename T>
-int tile_stream_launch_any(const AdmmArgs<T> &a, int KN, int KM, hipStream_t s)
+static int tile_stream_launch_any(const AdmmArgs<T> &a, int KN, int KM, hipStream_t s, const RefArgs *ref = nullptr)
 {
-#define MPCQ_TRY(KN_, KM_) if (KN == KN_ && KM == KM_) return tile_stream_launch<T, KN_, KM_>(a, s);
+#define MPCQ_TRY(KN_, KM_) if (KN == KN_ && KM == KM_) return tile_stream_launch<T, KN_, KM_>(a, s, ref);
     MPCQ_TILE_SHAPES(MPCQ_TRY)
 #undef MPCQ_TRY
     return -1;

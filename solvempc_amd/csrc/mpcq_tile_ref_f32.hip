@@ -1,0 +1,18 @@
+// solvempc_amd/csrc/mpcq_tile_ref_f32.hip — fp32 instantiations of the tile (MFMA) ADMM kernel's REF variant
+// (per-QP horizon references, RefArgs: mpcq_mpc_step_ref*, mpcq_mpc_run_ref_device).
+#define MPCQ_TILE_REF 1
+#include "mpcq_tile.h"
+
+extern "C" int mpcq_internal_tile_ref_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, const mpcq::RefArgs *ref,
+                                                 hipStream_t s)
+{
+    if (!ref || !ref->p) return -1;
+    return mpcq::tile_launch_any<float>(*a, KN, KM, s, ref);
+}
+
+extern "C" int mpcq_internal_tile_ref_stream_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM,
+                                                        const mpcq::RefArgs *ref, hipStream_t s)
+{
+    if (!ref || !ref->p) return -1;
+    return mpcq::tile_stream_launch_any<float>(*a, KN, KM, s, ref);
+}

@@ -142,9 +142,28 @@ __device__ __noinline__ void build_minv(const T *ops, const int *ctype, const Op
     }
 }
 
+// A translation unit that defines MPCQ_WAVE_REF before this header (mpcq_wave_ref_*.hip) compiles the same
+// kernel text as admm_wave_ref_kernel / stream_wave_ref_kernel, which read per-QP horizon references
+// (RefArgs, a trailing kernel argument); the scalar units' kernels keep their names, arguments and code
+// (as in mpcq_tile.h: a split per unit, not a shared body behind a wrapper).
+#ifdef MPCQ_WAVE_REF
+#define MPCQ_WAVE_KERNEL admm_wave_ref_kernel
+#define MPCQ_WAVE_STREAM_KERNEL stream_wave_ref_kernel
+#define MPCQ_WAVE_REF_PARAM , RefArgs ref
+#define MPCQ_WAVE_REF_ARG(r) , *(r)
+#define MPCQ_WAVE_SOLVE_PARAM , const RefArgs &ref, int kstep  // (wave_solve_one: kstep, a stream launch's control step)
+#define MPCQ_WAVE_SOLVE_ARG(k) , ref, k
+#else
+#define MPCQ_WAVE_KERNEL admm_wave_kernel
+#define MPCQ_WAVE_STREAM_KERNEL stream_wave_kernel
+#define MPCQ_WAVE_REF_PARAM
+#define MPCQ_WAVE_REF_ARG(r)
+#define MPCQ_WAVE_SOLVE_PARAM
+#define MPCQ_WAVE_SOLVE_ARG(k)
+#endif
 template <typename T, int NCAP, int MCAP, bool ALL_INEQ, bool LFREE>
 __device__ __forceinline__ void wave_solve_one(const AdmmArgs<T> &a, int nc, int mc, int b, T *bcx, T *bcw, double *mi,
-                                               bool fresh_ok = true)
+                                               bool fresh_ok MPCQ_WAVE_SOLVE_PARAM)
 {
     constexpr int VEC = 16 / sizeof(T);
     constexpr int BN = (NCAP + VEC - 1) / VEC * VEC, BM = (MCAP + VEC - 1) / VEC * VEC;
@@ -195,7 +214,13 @@ __device__ __forceinline__ void wave_solve_one(const AdmmArgs<T> &a, int nc, int
             for (int t = 0; t < 8; t++)
                 if (t < a.nx) s0 += fx[t] * Xv[t];
             const double s1 = a.Fu[pp * n + lane] * Uv;
+#ifdef MPCQ_WAVE_REF
+            const double *rrow = ref.row(b);
+            const long long r0 = ref.first(kstep);
+            for (int t = 0; t < n; t++) s2 += fr[t] * ref.at(rrow, r0, t);
+#else
             for (int t = 0; t < n; t++) s2 += fr[t] * a.xref;
+#endif
             qk = s0 + s1 + s2;
             a.q_out[(size_t)b * n + lane] = qk;
         } else {
@@ -555,7 +580,7 @@ __device__ __forceinline__ void wave_solve_one(const AdmmArgs<T> &a, int nc, int
 }
 
 template <typename T, int NCAP, int MCAP, bool ALL_INEQ, bool LFREE>
-__global__ __launch_bounds__(64, 2) void admm_wave_kernel(AdmmArgs<T> a, int nc, int mc)
+__global__ __launch_bounds__(64, 2) void MPCQ_WAVE_KERNEL(AdmmArgs<T> a, int nc, int mc MPCQ_WAVE_REF_PARAM)
 {
     static_assert(NCAP <= 64 && MCAP <= 64, "one row per lane");  // one wave per workgroup (wave_sync)
     constexpr int VEC = 16 / sizeof(T);
@@ -571,11 +596,12 @@ __global__ __launch_bounds__(64, 2) void admm_wave_kernel(AdmmArgs<T> a, int nc,
         const int sg = blockIdx.x % ListSeg::kShards, per = gridDim.x / ListSeg::kShards;
         const int count = a.count_in[sg * ListSeg::kStride];
         for (int slot = blockIdx.x / ListSeg::kShards; slot < count; slot += per)  // uniform: one wave per block
-            wave_solve_one<T, NCAP, MCAP, ALL_INEQ, LFREE>(a, nc, mc, a.list_in[sg * a.list_seg + slot], bcx, bcw, mi);
+            wave_solve_one<T, NCAP, MCAP, ALL_INEQ, LFREE>(a, nc, mc, a.list_in[sg * a.list_seg + slot], bcx, bcw, mi,
+                                                           true MPCQ_WAVE_SOLVE_ARG(0));
         return;
     }
     for (int slot = blockIdx.x; slot < a.batch; slot += gridDim.x)  // uniform: one wave per block
-        wave_solve_one<T, NCAP, MCAP, ALL_INEQ, LFREE>(a, nc, mc, a.qp0 + slot, bcx, bcw, mi);
+        wave_solve_one<T, NCAP, MCAP, ALL_INEQ, LFREE>(a, nc, mc, a.qp0 + slot, bcx, bcw, mi, true MPCQ_WAVE_SOLVE_ARG(0));
 }
 
 
@@ -588,11 +614,13 @@ __global__ __launch_bounds__(64, 2) void admm_wave_kernel(AdmmArgs<T> a, int nc,
 // per-step path's (wave_solve_one, sim_row), so the trajectory is bit-identical to it.  The state
 // (x', z, y, rho, X, U) goes through HBM between steps as it does between launches; one wave writes
 // and reads it, ordered by workgroup-scope fences (the workgroup is this one wave).
+// (stream_wave_ref_kernel, the MPCQ_WAVE_REF units: step k reads the reference window of schedule step
+// first_step + k.)
 template <typename T, int NCAP, int MCAP, bool ALL_INEQ, bool LFREE>
 #ifndef MPCQ_STREAM_WPE
 #define MPCQ_STREAM_WPE 2
 #endif
-__global__ __launch_bounds__(64, MPCQ_STREAM_WPE) void stream_wave_kernel(AdmmArgs<T> a, int nc, int mc, StreamArgs sa)
+__global__ __launch_bounds__(64, MPCQ_STREAM_WPE) void MPCQ_WAVE_STREAM_KERNEL(AdmmArgs<T> a, int nc, int mc, StreamArgs sa MPCQ_WAVE_REF_PARAM)
 {
     static_assert(NCAP <= 64 && MCAP <= 64, "one row per lane");
     constexpr int VEC = 16 / sizeof(T);
@@ -607,7 +635,7 @@ __global__ __launch_bounds__(64, MPCQ_STREAM_WPE) void stream_wave_kernel(AdmmAr
         const double *Ad = sa.Ad + (sa.shared ? 0 : (size_t)b * nx * nx);
         const double *Bd = sa.Bd + (sa.shared ? 0 : (size_t)b * nx);
         for (int k = 0; k < sa.steps; k++) {
-            wave_solve_one<T, NCAP, MCAP, ALL_INEQ, LFREE>(a, nc, mc, b, bcx, bcw, mi, k == 0);
+            wave_solve_one<T, NCAP, MCAP, ALL_INEQ, LFREE>(a, nc, mc, b, bcx, bcw, mi, k == 0 MPCQ_WAVE_SOLVE_ARG(k));
             __threadfence_block();  // this step's U (lane 0) and state before the plant update reads them
             double x[8];
 #pragma unroll
@@ -622,23 +650,25 @@ __global__ __launch_bounds__(64, MPCQ_STREAM_WPE) void stream_wave_kernel(AdmmAr
     }
 }
 
+// (The launchers that name the MPCQ_WAVE_* kernels are static: a scalar and a REF unit each keep their own.
+// ref: the REF units' trailing kernel argument, unused in the scalar ones.)
 template <typename T, int NCAP, int MCAP>
-int stream_launch(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa, hipStream_t s)
+static int stream_launch(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa, hipStream_t s, const RefArgs *ref = nullptr)
 {
     if (a.all_ineq && a.lower_free)
-        hipLaunchKernelGGL((stream_wave_kernel<T, NCAP, MCAP, true, true>), dim3(a.batch), dim3(64), 0, s, a, nc, mc, sa);
+        hipLaunchKernelGGL((MPCQ_WAVE_STREAM_KERNEL<T, NCAP, MCAP, true, true>), dim3(a.batch), dim3(64), 0, s, a, nc, mc, sa MPCQ_WAVE_REF_ARG(ref));
     else
-        hipLaunchKernelGGL((stream_wave_kernel<T, NCAP, MCAP, false, false>), dim3(a.batch), dim3(64), 0, s, a, nc, mc, sa);
+        hipLaunchKernelGGL((MPCQ_WAVE_STREAM_KERNEL<T, NCAP, MCAP, false, false>), dim3(a.batch), dim3(64), 0, s, a, nc, mc, sa MPCQ_WAVE_REF_ARG(ref));
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 template <typename T, int NCAP, int MCAP>
-int wave_launch(const AdmmArgs<T> &a, int nc, int mc, int grid, hipStream_t s)
+static int wave_launch(const AdmmArgs<T> &a, int nc, int mc, int grid, hipStream_t s, const RefArgs *ref = nullptr)
 {
     if (a.all_ineq && a.lower_free)
-        hipLaunchKernelGGL((admm_wave_kernel<T, NCAP, MCAP, true, true>), dim3(grid), dim3(64), 0, s, a, nc, mc);
+        hipLaunchKernelGGL((MPCQ_WAVE_KERNEL<T, NCAP, MCAP, true, true>), dim3(grid), dim3(64), 0, s, a, nc, mc MPCQ_WAVE_REF_ARG(ref));
     else
-        hipLaunchKernelGGL((admm_wave_kernel<T, NCAP, MCAP, false, false>), dim3(grid), dim3(64), 0, s, a, nc, mc);
+        hipLaunchKernelGGL((MPCQ_WAVE_KERNEL<T, NCAP, MCAP, false, false>), dim3(grid), dim3(64), 0, s, a, nc, mc MPCQ_WAVE_REF_ARG(ref));
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -646,7 +676,7 @@ int wave_launch(const AdmmArgs<T> &a, int nc, int mc, int grid, hipStream_t s)
 #define MPCQ_WAVE_CAPS(X) X(8, 16) X(16, 32) X(20, 40) X(32, 64)
 
 template <typename T>
-int wave_launch_any(const AdmmArgs<T> &a, int nc, int mc, int grid, hipStream_t s)
+static int wave_launch_any(const AdmmArgs<T> &a, int nc, int mc, int grid, hipStream_t s, const RefArgs *ref = nullptr)
 {
     int best = -1, bn = 0, bm = 0;
 #define MPCQ_PICK(NC_, MC_)                                                  \
@@ -655,14 +685,14 @@ int wave_launch_any(const AdmmArgs<T> &a, int nc, int mc, int grid, hipStream_t 
     }
     MPCQ_WAVE_CAPS(MPCQ_PICK)
 #undef MPCQ_PICK
-#define MPCQ_TRY(NC_, MC_) if (bn == NC_ && bm == MC_) return wave_launch<T, NC_, MC_>(a, nc, mc, grid, s);
+#define MPCQ_TRY(NC_, MC_) if (bn == NC_ && bm == MC_) return wave_launch<T, NC_, MC_>(a, nc, mc, grid, s, ref);
     MPCQ_WAVE_CAPS(MPCQ_TRY)
 #undef MPCQ_TRY
     return -1;
 }
 
 template <typename T>
-int stream_launch_any(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa, hipStream_t s)
+static int stream_launch_any(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa, hipStream_t s, const RefArgs *ref = nullptr)
 {
     int best = -1, bn = 0, bm = 0;
 #define MPCQ_PICK(NC_, MC_)                                                  \
@@ -671,7 +701,7 @@ int stream_launch_any(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa
     }
     MPCQ_WAVE_CAPS(MPCQ_PICK)
 #undef MPCQ_PICK
-#define MPCQ_TRY(NC_, MC_) if (bn == NC_ && bm == MC_) return stream_launch<T, NC_, MC_>(a, nc, mc, sa, s);
+#define MPCQ_TRY(NC_, MC_) if (bn == NC_ && bm == MC_) return stream_launch<T, NC_, MC_>(a, nc, mc, sa, s, ref);
     MPCQ_WAVE_CAPS(MPCQ_TRY)
 #undef MPCQ_TRY
     return -1;

@@ -98,6 +98,7 @@ class ModelPredictiveControlAPI:
         self.U = np.zeros(self.batch)
         self.t0 = 0.0
         self.dt = 0.0
+        self.ref_trajectory = None  # setRefTrajectory: (N,) or (batch, N) horizon reference, None: xref 1
         self.setSystemVars()
         self.setCosts()
         self._ops = condense({"Ad": self.Ad[None], "Bd": self.Bd.reshape(1, -1), "Cd": self.Cd.reshape(1, -1),
@@ -140,16 +141,33 @@ class ModelPredictiveControlAPI:
     def updateRef(self, pos_ref: float) -> None:
         self.ref = np.full(self.N, float(pos_ref))
 
+    def setRefTrajectory(self, ref) -> None:
+        """A horizon reference with preview in place of ``xref 1`` (no counterpart in the reference, which
+        tracks one set-point): ``(N,)`` shared by every copy, ``(batch, N)`` one per copy, or ``None`` to
+        return to ``updateRef(xref)``.  ``controllerStep`` then steps through ``mpc_step_ref`` and ``setF``
+        uses it."""
+        if ref is None:
+            self.ref_trajectory = None
+            return
+        ref = np.array(ref, dtype=np.float64)
+        if ref.shape not in ((self.N,), (self.batch, self.N)):
+            raise ValueError(f"ref of shape {ref.shape}: ({self.N},) or ({self.batch}, {self.N})")
+        self.ref_trajectory = ref
+
     def setF(self) -> None:
         """q = Fx X + Fu U + Fr ref' for every copy (ModelPredictiveControlAPI.cpp:372-375)."""
-        self.f = self.X @ self.Fx.T + self.U[:, None] * self.Fu + self.Fr @ self.ref
+        ref = self.ref if self.ref_trajectory is None else self.ref_trajectory
+        self.f = self.X @ self.Fx.T + self.U[:, None] * self.Fu + (self.Fr @ ref if ref.ndim == 1 else ref @ self.Fr.T)
 
     def controllerStep(self) -> bool:
         """One receding-horizon step (ModelPredictiveControlAPI.cpp:81-108) for every copy: q, u,
         warm-started solve, U += x[0].  False when any copy's solve did not reach OSQP_SOLVED."""
         self.t0 += self.dt
         self.updateRef(self.xref)
-        self.U = self.solver.mpc_step(self.X, self.U, self.xref)
+        if self.ref_trajectory is not None:
+            self.U = self.solver.mpc_step_ref(self.X, self.U, self.ref_trajectory)
+        else:
+            self.U = self.solver.mpc_step(self.X, self.U, self.xref)
         status, _, _ = self.solver.info()
         return bool(np.all(status == _capi.SOLVED))
 
