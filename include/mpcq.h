@@ -264,8 +264,38 @@ int mpcq_get_stream_path(mpcq_ctx *ctx, int *kind);
 int mpcq_get_order(mpcq_ctx *ctx, int *ordered, int *order);
 /* Per-QP counters of the last mpcq_mpc_run_device call (host arrays of `batch` ints, synchronises):
  * the ADMM iterations of all its control steps, and the steps whose solve did not end SOLVED
- * (controllerStep returning false, :102, where the reference's loop would exit, solver.cpp:50). */
+ * (controllerStep returning false, :102, where the reference's loop would exit, solver.cpp:50).
+ * The per-step values behind these sums: mpcq_mpc_set_stream_log below. */
 int mpcq_mpc_stream_counters(mpcq_ctx *ctx, int *iters, int *unsolved);
+
+/* Per-step record of a receding-horizon stream.  Device pointers, caller-owned, fp64/int32, step-major:
+ * row r holds what the batch looked like after the control step with absolute index step0 + r:
+ *   U      [r*batch + b]            U_b after that step's controllerStep (the control the plant then sees;
+ *                                   unchanged from the row before where the step did not end SOLVED)
+ *   X      [(r*batch + b)*nx + i]   X_b after that step's plant update (what the next step measures)
+ *   status [r*batch + b]            MPCQ_* status of that step's solve
+ *   iter   [r*batch + b]            its ADMM iterations
+ * Any of the four may be NULL (not recorded).  b is the context's local QP index. */
+typedef struct mpcq_stream_log {
+    double *U, *X;
+    int *status, *iter;
+    long long rows;   /* capacity in control steps */
+    long long step0;  /* absolute control step stored in row 0 */
+} mpcq_stream_log;
+
+/* Attach (or with log == NULL / all four pointers NULL: detach) a record to the context.  It applies to
+ * every later mpcq_mpc_run_device / mpcq_mpc_run_ref_device call until it is detached, on all three stream
+ * paths (tile stream, one QP per wave, per-step graph) and every dtype: the call's k-th control step fills
+ * row first_step + k - step0, so chunked runs (first_step = 0, 7, 12, ...) fill one buffer.  The rows are
+ * exactly the X_dev / U_dev / mpcq_get_info values that steps = 1 calls would have shown after each step, bit
+ * for bit.  The one-launch stream kernels write them from their once-per-control-step code (additional kernel
+ * variants: without a record every launch, kernel and result is what it is otherwise); the per-step graph
+ * captures a small record kernel after each plant update.  The buffers are written by the kernels of the
+ * run's `stream` and must stay valid until that stream has finished.
+ * MPCQ_ERR_ARG: a pointer is set and rows < 1 or step0 < 0.  A run returns MPCQ_ERR_ARG, before anything is
+ * enqueued (X_dev, U_dev, the counters and the buffers untouched), when any of its rows would fall outside
+ * [0, rows).  Not served: MIMO (no stream) and mpcq_mpc_plants_step_device. */
+int mpcq_mpc_set_stream_log(mpcq_ctx *ctx, const mpcq_stream_log *log);
 
 /* Condensed-QP construction on device `device` for n_plants SISO plants (ModelPredictiveControlAPI
  * setTransformations / setLL / setLiftedCosts / setH / setFVars / setLinearConstraints /

@@ -62,6 +62,7 @@ class BatchSolver:
         ctx = C.c_void_p()
         _capi.check(lib().mpcq_create(C.byref(dims), C.byref(self.settings), C.byref(ctx)), "mpcq_create")
         self._ctx = ctx
+        self.device = int(device)
         self.nx = 0
 
     def close(self):
@@ -268,6 +269,60 @@ class BatchSolver:
         _capi.check(lib().mpcq_mpc_stream_counters(self._ctx, it.ctypes.data_as(C.POINTER(C.c_int)),
                                                    un.ctypes.data_as(C.POINTER(C.c_int))), "mpcq_mpc_stream_counters")
         return it, un
+
+    def mpc_set_stream_log(self, U_ptr: int = 0, X_ptr: int = 0, status_ptr: int = 0, iter_ptr: int = 0,
+                           rows: int = 0, step0: int = 0) -> None:
+        """Attach a per-step record to every later mpc_run_device / mpc_run_ref_device call (mpcq_mpc_set_stream_log):
+        device buffers, step-major, U (rows, batch) and X (rows, batch, nx) fp64, status and iter (rows, batch)
+        int32; any may be 0 (not recorded).  The control step with absolute index ``step0 + r`` fills row r.  All
+        zeros detaches."""
+        log = _capi.StreamLog(U_ptr or None, X_ptr or None, status_ptr or None, iter_ptr or None, int(rows), int(step0))
+        _capi.check(lib().mpcq_mpc_set_stream_log(self._ctx, C.byref(log)), "mpcq_mpc_set_stream_log")
+
+    def mpc_rollout(self, X, U, steps: int, seed: int, noise_std: float, xref: float = 0.0, sched=None,
+                    first_qp: int = 0, first_step: int = 0) -> dict:
+        """One logged receding-horizon stream from host X (batch, nx), U (batch): ``steps`` control steps in one
+        call, the whole closed-loop trajectory back.  ``sched`` (None: the scalar ``xref``) of shape (L,) is one
+        reference schedule shared by the batch, (batch, L) one per QP (mpc_run_ref_device).  Returns numpy arrays
+        ``U`` (steps, batch), ``X`` (steps, batch, nx), ``status``, ``iter`` (steps, batch) — row k: after control
+        step first_step + k — and the final state ``X_final`` (batch, nx), ``U_final`` (batch).  The record is
+        detached again on return."""
+        import torch
+
+        B, nx, steps = self.batch, self.nx, int(steps)
+        dev = torch.device("cuda", self.device)
+        Xd = torch.from_numpy(_c64(X).reshape(B, nx).copy()).to(dev)
+        Ud = torch.from_numpy(_c64(U).reshape(B).copy()).to(dev)
+        rows = max(steps, 1)
+        lU = torch.zeros(rows, B, dtype=torch.float64, device=dev)
+        lX = torch.zeros(rows, B, nx, dtype=torch.float64, device=dev)
+        lS = torch.zeros(rows, B, dtype=torch.int32, device=dev)
+        lI = torch.zeros(rows, B, dtype=torch.int32, device=dev)
+        sd = None
+        if sched is not None:
+            sc = _c64(sched)
+            if sc.ndim == 1:
+                stride = 0
+            elif sc.ndim == 2 and sc.shape[0] == B:
+                stride = sc.shape[1]
+            else:
+                raise ValueError(f"sched of shape {sc.shape}: (L,) or ({B}, L)")
+            sd = torch.from_numpy(sc.copy()).to(dev)
+        side = torch.cuda.Stream(device=dev)
+        torch.cuda.synchronize(dev)
+        self.mpc_set_stream_log(lU.data_ptr(), lX.data_ptr(), lS.data_ptr(), lI.data_ptr(), rows, first_step)
+        try:
+            if sd is None:
+                self.mpc_run_device(Xd.data_ptr(), Ud.data_ptr(), xref, steps, seed, first_qp, first_step, noise_std,
+                                    side.cuda_stream)
+            else:
+                self.mpc_run_ref_device(Xd.data_ptr(), Ud.data_ptr(), sd.data_ptr(), sc.shape[-1], stride, steps, seed,
+                                        first_qp, first_step, noise_std, side.cuda_stream)
+            side.synchronize()
+        finally:
+            self.mpc_set_stream_log()
+        return {"U": lU[:steps].cpu().numpy(), "X": lX[:steps].cpu().numpy(), "status": lS[:steps].cpu().numpy(),
+                "iter": lI[:steps].cpu().numpy(), "X_final": Xd.cpu().numpy(), "U_final": Ud.cpu().numpy()}
 
     def stream_iterations(self) -> np.ndarray:
         return self.stream_counters()[0]

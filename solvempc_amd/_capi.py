@@ -22,7 +22,7 @@ EXPORTS = (
     "mpcq_condense", "mpcq_mpc_setup_plants_device", "mpcq_last_error", "mpcq_get_path",
     "mpcq_mimo_setup_plants_device", "mpcq_mimo_step_device", "mpcq_mpc_stream_counters",
     "mpcq_mpc_plants_step_device", "mpcq_get_stream_path", "mpcq_get_order", "mpcq_get_polish_info",
-    "mpcq_mpc_step_ref_device", "mpcq_mpc_step_ref", "mpcq_mpc_run_ref_device",
+    "mpcq_mpc_step_ref_device", "mpcq_mpc_step_ref", "mpcq_mpc_run_ref_device", "mpcq_mpc_set_stream_log",
 )
 
 
@@ -53,6 +53,12 @@ class Dims(C.Structure):
 class DeviceView(C.Structure):
     _fields_ = [("q", C.c_void_p), ("u", C.c_void_p), ("l", C.c_void_p), ("x", C.c_void_p),
                 ("y", C.c_void_p), ("status", C.c_void_p), ("iter", C.c_void_p), ("rho", C.c_void_p)]
+
+
+class StreamLog(C.Structure):
+    """mpcq_stream_log: the per-step record of a receding-horizon stream (device pointers; rows, step0)."""
+    _fields_ = [("U", C.c_void_p), ("X", C.c_void_p), ("status", C.c_void_p), ("iter", C.c_void_p),
+                ("rows", C.c_longlong), ("step0", C.c_longlong)]
 
 
 _LIB = None
@@ -108,6 +114,7 @@ def lib() -> C.CDLL:
         "mpcq_mpc_run_device": (C.c_int, [vp, vp, vp, C.c_double, C.c_int, C.c_ulonglong, C.c_longlong,
                                           C.c_longlong, C.c_double, vp]),
         "mpcq_mpc_stream_counters": (C.c_int, [vp, ip, ip]),
+        "mpcq_mpc_set_stream_log": (C.c_int, [vp, C.POINTER(StreamLog)]),
         "mpcq_mpc_plants_step_device": (C.c_int, [vp, C.c_int, C.c_int] + [vp] * 9 + [C.c_double, vp]),
         "mpcq_condense": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 15),
         "mpcq_mpc_setup_plants_device": (C.c_int, [vp, C.c_int, C.c_int] + [vp] * 7 + [vp]),

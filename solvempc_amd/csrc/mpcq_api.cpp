@@ -155,6 +155,12 @@ struct mpcq_ctx {
     int *d_it_acc = nullptr, *d_uns_acc = nullptr;
     bool stream_acc = false;  // launches made inside mpcq_mpc_run_device accumulate into them
     int stream_path = MPCQ_STREAM_GRAPH;  // how the last mpcq_mpc_run_device call ran
+    // per-step record of the stream (mpcq_mpc_set_stream_log): the caller's buffers while one is attached
+    // (slog_on), baked into a captured graph (gen); d_logref: the one-entry schedule [xref] a logged scalar run
+    // hands the wave stream's REF + LOG kernel
+    mpcq_stream_log slog{};
+    bool slog_on = false;
+    double *d_logref = nullptr;
     // hardest-first order of a tile-path MPC step (mpcq_order.hip, build_order_map): the m x kStride
     // violation map of plant 0, the bin counters and lists; ord_ok when the map matches the current setup
     // and operators
@@ -548,7 +554,7 @@ int mpcq_destroy(mpcq_ctx *c)
                     c->d_Sbar, c->d_Ku, c->d_W0, c->d_X, c->d_U, c->d_img, c->d_list, c->d_counts,
                     c->d_itstate, c->d_Ad, c->d_Bd, c->d_step, c->d_flags, c->d_stamps, c->d_mimo,
                     c->d_it_acc, c->d_uns_acc, c->d_Xs, c->d_Us, c->d_ordmap, c->d_ord, c->d_pol_status,
-                    c->d_pol_nact, c->d_pol_res, c->d_ref, c->d_ordG};
+                    c->d_pol_nact, c->d_pol_res, c->d_ref, c->d_ordG, c->d_logref};
     if (c->gexec) (void)hipGraphExecDestroy(c->gexec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     for (void *p : ptrs)
@@ -1739,6 +1745,17 @@ int mpcq_mpc_stream_counters(mpcq_ctx *c, int *iters, int *unsolved)
     return d2h(c, unsolved, c->d_uns_acc, 4 * B);
 }
 
+int mpcq_mpc_set_stream_log(mpcq_ctx *c, const mpcq_stream_log *log)
+{
+    if (!c) return fail(MPCQ_ERR_ARG, "null context");
+    const bool on = log && (log->U || log->X || log->status || log->iter);
+    if (on && (log->rows < 1 || log->step0 < 0)) return fail(MPCQ_ERR_ARG, "stream log: rows >= 1 and step0 >= 0 required");
+    if (on || c->slog_on) c->gen++;  // (the record kernel and its buffers are baked into a captured graph)
+    c->slog = on ? *log : mpcq_stream_log{};
+    c->slog_on = on;
+    return MPCQ_OK;
+}
+
 int mpcq_mpc_simulate_device(mpcq_ctx *c, double *X, const double *U, unsigned long long seed, long long first_qp,
                              long long step, double noise_std, void *stream)
 {
@@ -1757,7 +1774,8 @@ int mpcq_mpc_simulate_device(mpcq_ctx *c, double *X, const double *U, unsigned l
 // steps with the plant update between them, no per-step launches or graph.
 }  // extern "C"
 template <typename T>
-static int launch_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, double xref, const mpcq::StreamArgs &sa)
+static int launch_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, double xref, const mpcq::StreamArgs &sa,
+                         const mpcq::LogArgs *lg)
 {
     c->xy_lazy = false;  // (the stream writes every QP's x, y at its last step)
     c->rho_lazy = false;  // (and rho)
@@ -1769,6 +1787,10 @@ static int launch_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, doubl
     // (a reference schedule, c->cur_ref: the REF variant slides the window with the step)
     a.stop_iter = c->set.max_iter;
     c->qu_lazy = false;
+    if (lg)  // a record is attached: the REF + LOG variant (a scalar run: the one-entry schedule [xref], mpc_run)
+        return std::is_same<T, float>::value
+                   ? mpcq_internal_stream_log_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, &sa, &c->cur_ref, lg, s)
+                   : mpcq_internal_stream_log_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, &sa, &c->cur_ref, lg, s);
     if (c->cur_ref.p)
         return std::is_same<T, float>::value
                    ? mpcq_internal_stream_ref_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, &sa, &c->cur_ref, s)
@@ -1787,7 +1809,8 @@ extern "C" {
 // on check iterations (multiples of check_termination, as OSQP's defaults are).
 }  // extern "C"
 template <typename T>
-static int launch_tile_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, double xref, mpcq::StreamArgs sa)
+static int launch_tile_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, double xref, mpcq::StreamArgs sa,
+                              const mpcq::LogArgs *lg)
 {
     c->xy_lazy = false;  // (the stream writes every QP's x, y at its last step)
     c->rho_lazy = false;  // (and rho)
@@ -1832,7 +1855,14 @@ static int launch_tile_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, 
         a.stamps = c->d_stamps;
     }
     const int rc =
-        c->cur_ref.p ? (std::is_same<T, float>::value
+        lg && c->cur_ref.p  // a record is attached: the REF kernel's LOG variant, or the scalar kernel's
+            ? (std::is_same<T, float>::value
+                   ? mpcq_internal_tile_reflog_stream_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, &c->cur_ref, lg, s)
+                   : mpcq_internal_tile_reflog_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, &c->cur_ref, lg, s))
+        : lg ? (std::is_same<T, float>::value
+                    ? mpcq_internal_tile_log_stream_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, lg, s)
+                    : mpcq_internal_tile_log_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, lg, s))
+        : c->cur_ref.p ? (std::is_same<T, float>::value
                        ? mpcq_internal_tile_ref_stream_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, &c->cur_ref, s)
                        : mpcq_internal_tile_ref_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, &c->cur_ref, s))
                 : (std::is_same<T, float>::value
@@ -1874,6 +1904,21 @@ static int mpc_run(mpcq_ctx *c, const char *fn, double *X, double *U, double xre
     if (!X || !U || steps < 0) return fail(MPCQ_ERR_ARG, "null X/U or steps < 0");
     if (!stream) return fail(MPCQ_ERR_ARG, "graph capture needs a non-NULL stream");
     hipStream_t s = (hipStream_t)stream;
+    // an attached record (mpcq_mpc_set_stream_log): every row of this run must lie in its buffers, checked before
+    // anything is enqueued.  The one-launch kernels index the rows from first_step themselves (lg_launch), the
+    // per-step launches from the device step counter (lg_graph), as with the reference window below.
+    const bool logged = c->slog_on && steps > 0;
+    mpcq::LogArgs lg_launch{}, lg_graph{};
+    if (logged) {
+        const mpcq_stream_log &L = c->slog;
+        if (first_step < L.step0 || first_step - L.step0 > L.rows - steps)
+            return fail(MPCQ_ERR_ARG, std::string(fn) + ": control steps outside the attached stream log's rows");
+        lg_launch = mpcq::LogArgs{L.U, L.X, L.status, L.iter, first_step - L.step0, nullptr, c->dims.batch};
+        lg_graph = mpcq::LogArgs{L.U, L.X, L.status, L.iter, -L.step0, c->d_step, c->dims.batch};
+        if (!sched && !c->d_logref && hipMalloc((void **)&c->d_logref, 8) != hipSuccess)
+            return fail(MPCQ_ERR_HIP, "hipMalloc failed");
+    }
+    const mpcq::LogArgs *const lgp = logged ? &lg_launch : nullptr;
     // the one-launch kernels slide the window from first_step themselves; the per-step launches (eager first
     // step, captured graph) take the step from the device counter, as the captured plant simulation does
     mpcq::RefArgs ref_launch{}, ref_graph{};
@@ -1908,8 +1953,8 @@ static int mpc_run(mpcq_ctx *c, const char *fn, double *X, double *U, double xre
     if (tile_ok) {
         const mpcq::StreamArgs sa{steps, c->nx, c->dims.n_plants == 1, 0, c->d_Ad, c->d_Bd, seed, first_qp, first_step,
                                   noise_std};
-        const int lrc = c->dims.dtype == MPCQ_F32 ? launch_tile_stream<float>(c, s, X, U, xref, sa)
-                                                  : launch_tile_stream<double>(c, s, X, U, xref, sa);
+        const int lrc = c->dims.dtype == MPCQ_F32 ? launch_tile_stream<float>(c, s, X, U, xref, sa, lgp)
+                                                  : launch_tile_stream<double>(c, s, X, U, xref, sa, lgp);
         if (lrc == -2) return fail(MPCQ_ERR_HIP, std::string("tile stream launch failed: ") + hipGetErrorString(hipGetLastError()));
         if (lrc == 0) {
             if (mpcq_internal_set_step(c->d_step, first_step + steps, s)) return fail(MPCQ_ERR_HIP, "set_step launch failed");
@@ -1923,8 +1968,14 @@ static int mpc_run(mpcq_ctx *c, const char *fn, double *X, double *U, double xre
         std::strcmp(smode, "graph") != 0) {
         const mpcq::StreamArgs sa{steps, c->nx, c->dims.n_plants == 1, 1, c->d_Ad, c->d_Bd, seed, first_qp, first_step,
                                   noise_std};
-        const int lrc = c->dims.dtype == MPCQ_F32 ? launch_stream<float>(c, s, X, U, xref, sa)
-                                                  : launch_stream<double>(c, s, X, U, xref, sa);
+        if (logged && !sched) {
+            // a logged scalar run: the wave stream has the REF kernel's LOG variant only, handed the shared
+            // one-entry schedule [xref] (a uniform reference reproduces the scalar path bit for bit)
+            if (mpcq_internal_fill(c->d_logref, 0, xref, 1, s)) return fail(MPCQ_ERR_HIP, "fill launch failed");
+            c->cur_ref = mpcq::RefArgs{c->d_logref, 0, first_step, nullptr, 1};
+        }
+        const int lrc = c->dims.dtype == MPCQ_F32 ? launch_stream<float>(c, s, X, U, xref, sa, lgp)
+                                                  : launch_stream<double>(c, s, X, U, xref, sa, lgp);
         if (lrc) return fail(MPCQ_ERR_HIP, std::string("stream kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
         if (mpcq_internal_set_step(c->d_step, first_step + steps, s)) return fail(MPCQ_ERR_HIP, "set_step launch failed");
         c->fresh = false;
@@ -1935,12 +1986,23 @@ static int mpc_run(mpcq_ctx *c, const char *fn, double *X, double *U, double xre
     int done = 0;
     c->stream_path = MPCQ_STREAM_GRAPH;
     c->cur_ref = ref_graph;
+    // the record's row of a per-step launch, after its plant update and ahead of the counter's tick: the kernel
+    // reads the published status, iter, so an ordered tile solve's list-slot pairs are permuted first
+    // (materialize_info, on the same stream: captured with the step)
+    auto log_row = [&]() -> int {
+        if (!logged) return MPCQ_OK;
+        if (int mrc = materialize_info(c)) return mrc;
+        if (mpcq_internal_log_row(c->nx, X, U, c->d_status, c->d_iter, &lg_graph, s))
+            return fail(MPCQ_ERR_HIP, "stream log kernel launch failed");
+        return MPCQ_OK;
+    };
     if (c->fresh) {  // a reset is a one-off (x = z = y = 0): run that step eagerly, capture the rest
         if ((rc = launch_solve(c, s, true, X, U, xref))) return rc;
         if (mpcq_internal_simulate(c->dims.batch, c->nx, c->dims.n_plants == 1, c->d_Ad, c->d_Bd, X, U, seed,
-                                   first_qp, c->d_step, 0, noise_std, s) ||
-            mpcq_internal_tick(c->d_step, s))
+                                   first_qp, c->d_step, 0, noise_std, s))
             return fail(MPCQ_ERR_HIP, "simulate kernel launch failed");
+        if ((rc = log_row())) return rc;
+        if (mpcq_internal_tick(c->d_step, s)) return fail(MPCQ_ERR_HIP, "simulate kernel launch failed");
         done = 1;
         if ((rc = stage("eager first step"))) return rc;
     }
@@ -1953,10 +2015,11 @@ static int mpc_run(mpcq_ctx *c, const char *fn, double *X, double *U, double xre
         if (c->graph) { (void)hipGraphDestroy(c->graph); c->graph = nullptr; }
         HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         int lrc = launch_solve(c, s, true, X, U, xref);
-        if (!lrc && (mpcq_internal_simulate(c->dims.batch, c->nx, c->dims.n_plants == 1, c->d_Ad, c->d_Bd, X, U,
-                                            seed, first_qp, c->d_step, 0, noise_std, s) ||
-                     mpcq_internal_tick(c->d_step, s)))
+        if (!lrc && mpcq_internal_simulate(c->dims.batch, c->nx, c->dims.n_plants == 1, c->d_Ad, c->d_Bd, X, U,
+                                           seed, first_qp, c->d_step, 0, noise_std, s))
             lrc = fail(MPCQ_ERR_HIP, "simulate kernel launch failed");
+        if (!lrc) lrc = log_row();
+        if (!lrc && mpcq_internal_tick(c->d_step, s)) lrc = fail(MPCQ_ERR_HIP, "simulate kernel launch failed");
         hipGraph_t g = nullptr;
         const hipError_t ec = hipStreamEndCapture(s, &g);
         // a discarded capture ran none of its launches: the phase-list counters are not known clean

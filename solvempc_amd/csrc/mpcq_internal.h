@@ -196,6 +196,26 @@ struct RefArgs {
     }
 };
 
+// Per-step record of a receding-horizon stream (mpcq_mpc_set_stream_log; written by the LOG kernel variants
+// and the per-step graph's record kernel only).  Step-major: the launch's k-th control step fills row
+//     r = row0 + k (+ *step_p where non-null),   U, status, iter at [r batch + b], X at [(r batch + b) nx + i]
+// with row0 = first_step - step0 for a one-launch stream (k = 0 .. steps - 1) and row0 = -step0, k = 0 for the
+// per-step graph, whose step is the context's device step counter (step_p).  The host has checked every row of
+// the run against the buffers' capacity before anything is enqueued.  A null array is not recorded.
+// Like RefArgs it is a kernel argument of its own: the scalar and REF kernels' arguments (and code) are what
+// they were.
+struct LogArgs {
+    double *U, *X;
+    int *status, *iter;
+    long long row0;
+    const long long *step_p;
+    int batch;
+    __device__ __forceinline__ size_t at(int k, int b) const
+    {
+        return (size_t)((step_p ? *step_p : 0) + row0 + k) * (size_t)batch + (size_t)b;
+    }
+};
+
 template <typename T>
 struct AdmmArgs {
     int batch, n, m;
@@ -507,6 +527,26 @@ int mpcq_internal_stream_ref_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, 
                                         const mpcq::RefArgs *ref, hipStream_t s);
 int mpcq_internal_stream_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const mpcq::StreamArgs *sa,
                                         const mpcq::RefArgs *ref, hipStream_t s);
+// The one-launch streams with a per-step record: the stream kernels compiled once more with LogArgs as a further
+// trailing kernel argument.  Tile: the scalar kernel's LOG variant (mpcq_tile_log_*.hip) and the REF kernel's
+// (mpcq_tile_reflog_*.hip).  One QP per wave: the REF kernel's only (mpcq_wave_log_*.hip), which a scalar-xref run
+// hands the one-entry schedule [xref].  Same return codes; -1 also for a null reference or record.
+int mpcq_internal_tile_log_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, const mpcq::LogArgs *lg,
+                                             hipStream_t s);
+int mpcq_internal_tile_log_stream_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, const mpcq::LogArgs *lg,
+                                             hipStream_t s);
+int mpcq_internal_tile_reflog_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, const mpcq::RefArgs *ref,
+                                                const mpcq::LogArgs *lg, hipStream_t s);
+int mpcq_internal_tile_reflog_stream_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, const mpcq::RefArgs *ref,
+                                                const mpcq::LogArgs *lg, hipStream_t s);
+int mpcq_internal_stream_log_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const mpcq::StreamArgs *sa,
+                                        const mpcq::RefArgs *ref, const mpcq::LogArgs *lg, hipStream_t s);
+int mpcq_internal_stream_log_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const mpcq::StreamArgs *sa,
+                                        const mpcq::RefArgs *ref, const mpcq::LogArgs *lg, hipStream_t s);
+// One row of the record from the context's buffers (mpcq_log.hip; the per-step graph, after the step's plant
+// update): U, X as they stand, status and iter of the step's solve.
+int mpcq_internal_log_row(int nx, const double *X, const double *U, const int *status, const int *iter,
+                          const mpcq::LogArgs *lg, hipStream_t s);
 // Plant update of the receding-horizon stream (mpcq_stream.hip); step from *step_p when non-null.
 int mpcq_internal_simulate(int batch, int nx, int shared, const double *Ad, const double *Bd, double *X,
                            const double *U, unsigned long long seed, long long first_qp, const long long *step_p,

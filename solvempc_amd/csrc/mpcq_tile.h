@@ -478,14 +478,32 @@ __device__ __forceinline__ void reg_mv(const T (&m1)[kRegMvTiles<T, REM, NTO>][K
 // and not a template parameter or a shared body function so that admm_tile_kernel's instantiations keep
 // their names and their code: a wrapper around a shared body moved the register allocation of the scalar
 // stream kernel (2 % slower).
-#ifdef MPCQ_TILE_REF
+// LOG (MPCQ_TILE_LOG, alone or on top of MPCQ_TILE_REF: mpcq_tile_log_*.hip, mpcq_tile_reflog_*.hip;
+// mpcq_mpc_set_stream_log): the scalar or the REF kernel text compiled once more as admm_tile_log_kernel /
+// admm_tile_reflog_kernel, whose stream mode writes the per-step record (LogArgs, the last kernel argument) from
+// its once-per-control-step code: U, status and iter of a column's finished step at its finalize (lane group 0),
+// the plant's new X in stream_next (lane group g: components g, g + 4).  Those units instantiate the stream
+// launchers only.
+#if defined(MPCQ_TILE_LOG) && defined(MPCQ_TILE_REF)
+#define MPCQ_TILE_KERNEL admm_tile_reflog_kernel
+#define MPCQ_TILE_REF_PARAM , RefArgs ref, LogArgs lg
+#define MPCQ_TILE_REF_ARG(r) , *(r)
+#define MPCQ_TILE_LOG_ARG(l) , *(l)
+#elif defined(MPCQ_TILE_LOG)
+#define MPCQ_TILE_KERNEL admm_tile_log_kernel
+#define MPCQ_TILE_REF_PARAM , LogArgs lg
+#define MPCQ_TILE_REF_ARG(r)
+#define MPCQ_TILE_LOG_ARG(l) , *(l)
+#elif defined(MPCQ_TILE_REF)
 #define MPCQ_TILE_KERNEL admm_tile_ref_kernel
 #define MPCQ_TILE_REF_PARAM , RefArgs ref
 #define MPCQ_TILE_REF_ARG(r) , *(r)
+#define MPCQ_TILE_LOG_ARG(l)
 #else
 #define MPCQ_TILE_KERNEL admm_tile_kernel
 #define MPCQ_TILE_REF_PARAM
 #define MPCQ_TILE_REF_ARG(r)
+#define MPCQ_TILE_LOG_ARG(l)
 #endif
 template <typename T, int KN, int KM, bool ALL_INEQ, bool LFREE, int G, int OCC, bool PAIRED = false, int WPB = 4,
           bool STREAM = false, bool MIX = false>
@@ -496,6 +514,13 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
 #else
     constexpr bool REF = false;
     const RefArgs ref{};  // (never read: every use is under `if constexpr (REF)`)
+#endif
+#ifdef MPCQ_TILE_LOG
+    constexpr bool LOG = true;
+    static_assert(STREAM && G == 1, "the record is the stream mode's");
+#else
+    constexpr bool LOG = false;
+    const LogArgs lg{};  // (never read: every use is under `if constexpr (LOG)`)
 #endif
     MPCQ_TSTAMP(0, (long long)__builtin_amdgcn_s_memtime());
     MPCQ_TSTAMP(6, (long long)__builtin_amdgcn_s_memrealtime());
@@ -811,7 +836,15 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
                 uu = up[s] * e;
                 if constexpr (!LFREE) ll = lo[s] * e;
                 if (!resume) {  // a resumed phase's QPs passed these checks in phase 0
-                    if (uu < ll) bad = 1;
+                    if (uu < ll) {
+                        // (LFREE: l is not loaded and ll stands for a free bound, so a u^ below -OSQP_INFTY lands
+                        // here though u >= l; the row's own l decides, as in the wave and lane kernels.  Cold.)
+                        if constexpr (LFREE) {
+                            if (uu < a.l[(a.l_shared ? 0 : (size_t)b * m) + v] * e) bad = 1;
+                        } else {
+                            bad = 1;
+                        }
+                    }
                     if constexpr (ALL_INEQ && LFREE) {
                         if (uu > kInfty * kMinScaling) tchg = 1;  // a free row: not the setup's type
                     } else {
@@ -935,6 +968,14 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
                 const double u1 = (a.mpc_u && sta == kSolved) ? pst[8] + x0 : pst[8];
                 pst[8] = u1;
                 if (full && g == 0) o_U[b] = u1;
+                if constexpr (LOG) {  // the record's row of this control step (every step, not only the full one)
+                    if (g == 0) {
+                        const size_t e = lg.at(kst[gi], b);
+                        if (lg.U) lg.U[e] = u1;
+                        if (lg.status) lg.status[e] = sta;
+                        if (lg.iter) lg.iter[e] = it - cst[gi];
+                    }
+                }
             }
             const bool keep = has_sol || sta == kInvalidBounds || sta == kTypeChanged;
             if (!full) {
@@ -1017,6 +1058,13 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
                 for (int t = 0; t < 8; t++) {
                     const double v = col_from(t < 4 ? x0 : x1, t & 3, g);
                     if (fin) pst[t] = t < nx ? v : 0.0;
+                }
+                if constexpr (LOG) {  // the record's X of the step just finished
+                    if (fin && lg.X) {
+                        double *const Xr = lg.X + lg.at(kst[0], b) * (size_t)nx;
+                        if (g < nx) Xr[g] = x0;
+                        if (g + 4 < nx) Xr[g + 4] = x1;
+                    }
                 }
                 bool fill[G];
                 fill[0] = fin && kst[0] + 1 < a.sim.steps;
@@ -2063,7 +2111,7 @@ static int tile_launch_variant(const AdmmArgs<T> &a, hipStream_t s, unsigned lds
 // The receding-horizon stream in one launch (AdmmArgs::sim): the paired condensed-MPC shape only
 // (-1 otherwise: the caller replays per-step launches).
 template <typename T, int KN, int KM>
-static int tile_stream_launch(const AdmmArgs<T> &a, hipStream_t s, const RefArgs *ref = nullptr)
+static int tile_stream_launch(const AdmmArgs<T> &a, hipStream_t s, const RefArgs *ref = nullptr, const LogArgs *lg = nullptr)
 {
     if constexpr (KM == 2 * KN) {
         if (a.paired && a.all_ineq && a.lower_free) {
@@ -2076,16 +2124,16 @@ static int tile_stream_launch(const AdmmArgs<T> &a, hipStream_t s, const RefArgs
             if constexpr (std::is_same<T, double>::value) {
                 if (a.mix_r > 0) {  // MPCQ_F64_MIXED: each step's plain iterations before the last mix_r in fp32
                     if (a.sim.occ == 1)
-                        hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 1, true, WPB, true, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref));
+                        hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 1, true, WPB, true, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref) MPCQ_TILE_LOG_ARG(lg));
                     else
-                        hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 2, true, WPB, true, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref));
+                        hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 2, true, WPB, true, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref) MPCQ_TILE_LOG_ARG(lg));
                     return hipGetLastError() == hipSuccess ? 0 : -2;
                 }
             }
             if (a.sim.occ == 1)
-                hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 1, true, WPB, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref));
+                hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 1, true, WPB, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref) MPCQ_TILE_LOG_ARG(lg));
             else
-                hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 2, true, WPB, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref));
+                hipLaunchKernelGGL((MPCQ_TILE_KERNEL<T, KN, KM, true, true, 1, 2, true, WPB, true>), grid, block, 0, s, a MPCQ_TILE_REF_ARG(ref) MPCQ_TILE_LOG_ARG(lg));
             return hipGetLastError() == hipSuccess ? 0 : -2;
         }
     }
@@ -2191,9 +2239,10 @@ int tile_publish_any(const AdmmArgs<T> &a, int KN, int KM, bool paired, hipStrea
 }
 
 template <typename T>
-static int tile_stream_launch_any(const AdmmArgs<T> &a, int KN, int KM, hipStream_t s, const RefArgs *ref = nullptr)
+static int tile_stream_launch_any(const AdmmArgs<T> &a, int KN, int KM, hipStream_t s, const RefArgs *ref = nullptr,
+                                  const LogArgs *lg = nullptr)
 {
-#define MPCQ_TRY(KN_, KM_) if (KN == KN_ && KM == KM_) return tile_stream_launch<T, KN_, KM_>(a, s, ref);
+#define MPCQ_TRY(KN_, KM_) if (KN == KN_ && KM == KM_) return tile_stream_launch<T, KN_, KM_>(a, s, ref, lg);
     MPCQ_TILE_SHAPES(MPCQ_TRY)
 #undef MPCQ_TRY
     return -1;

@@ -146,9 +146,25 @@ __device__ __noinline__ void build_minv(const T *ops, const int *ctype, const Op
 // kernel text as admm_wave_ref_kernel / stream_wave_ref_kernel, which read per-QP horizon references
 // (RefArgs, a trailing kernel argument); the scalar units' kernels keep their names, arguments and code
 // (as in mpcq_tile.h: a split per unit, not a shared body behind a wrapper).
+// MPCQ_WAVE_LOG on top of MPCQ_WAVE_REF (mpcq_wave_log_*.hip; mpcq_mpc_set_stream_log): the REF stream kernel's text
+// once more as stream_wave_reflog_kernel, which writes the per-step record (LogArgs, a further trailing argument)
+// after each control step's fences.  Those units instantiate the stream launcher only.
+#if defined(MPCQ_WAVE_LOG) && !defined(MPCQ_WAVE_REF)
+#error "MPCQ_WAVE_LOG builds on MPCQ_WAVE_REF"
+#endif
+#ifdef MPCQ_WAVE_LOG
+#define MPCQ_WAVE_STREAM_KERNEL stream_wave_reflog_kernel
+#define MPCQ_WAVE_LOG_PARAM , LogArgs lg
+#define MPCQ_WAVE_LOG_ARG(l) , *(l)
+#else
+#define MPCQ_WAVE_LOG_PARAM
+#define MPCQ_WAVE_LOG_ARG(l)
+#endif
 #ifdef MPCQ_WAVE_REF
 #define MPCQ_WAVE_KERNEL admm_wave_ref_kernel
+#ifndef MPCQ_WAVE_LOG
 #define MPCQ_WAVE_STREAM_KERNEL stream_wave_ref_kernel
+#endif
 #define MPCQ_WAVE_REF_PARAM , RefArgs ref
 #define MPCQ_WAVE_REF_ARG(r) , *(r)
 #define MPCQ_WAVE_SOLVE_PARAM , const RefArgs &ref, int kstep  // (wave_solve_one: kstep, a stream launch's control step)
@@ -620,7 +636,7 @@ template <typename T, int NCAP, int MCAP, bool ALL_INEQ, bool LFREE>
 #ifndef MPCQ_STREAM_WPE
 #define MPCQ_STREAM_WPE 2
 #endif
-__global__ __launch_bounds__(64, MPCQ_STREAM_WPE) void MPCQ_WAVE_STREAM_KERNEL(AdmmArgs<T> a, int nc, int mc, StreamArgs sa MPCQ_WAVE_REF_PARAM)
+__global__ __launch_bounds__(64, MPCQ_STREAM_WPE) void MPCQ_WAVE_STREAM_KERNEL(AdmmArgs<T> a, int nc, int mc, StreamArgs sa MPCQ_WAVE_REF_PARAM MPCQ_WAVE_LOG_PARAM)
 {
     static_assert(NCAP <= 64 && MCAP <= 64, "one row per lane");
     constexpr int VEC = 16 / sizeof(T);
@@ -646,6 +662,16 @@ __global__ __launch_bounds__(64, MPCQ_STREAM_WPE) void MPCQ_WAVE_STREAM_KERNEL(A
                                         : 0.0;
             if (lane < nx) const_cast<double *>(a.X)[(size_t)b * nx + lane] = xn;
             __threadfence_block();  // the next step's front end reads X
+#ifdef MPCQ_WAVE_LOG
+            // the record's row of this control step, from the values just passed through memory
+            const size_t e = lg.at(k, b);
+            if (lane == 0) {
+                if (lg.U) lg.U[e] = u;
+                if (lg.status) lg.status[e] = a.status[b];
+                if (lg.iter) lg.iter[e] = a.iter[b];
+            }
+            if (lane < nx && lg.X) lg.X[e * (size_t)nx + lane] = xn;
+#endif
         }
     }
 }
@@ -653,12 +679,13 @@ __global__ __launch_bounds__(64, MPCQ_STREAM_WPE) void MPCQ_WAVE_STREAM_KERNEL(A
 // (The launchers that name the MPCQ_WAVE_* kernels are static: a scalar and a REF unit each keep their own.
 // ref: the REF units' trailing kernel argument, unused in the scalar ones.)
 template <typename T, int NCAP, int MCAP>
-static int stream_launch(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa, hipStream_t s, const RefArgs *ref = nullptr)
+static int stream_launch(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa, hipStream_t s, const RefArgs *ref = nullptr,
+                         const LogArgs *lg = nullptr)
 {
     if (a.all_ineq && a.lower_free)
-        hipLaunchKernelGGL((MPCQ_WAVE_STREAM_KERNEL<T, NCAP, MCAP, true, true>), dim3(a.batch), dim3(64), 0, s, a, nc, mc, sa MPCQ_WAVE_REF_ARG(ref));
+        hipLaunchKernelGGL((MPCQ_WAVE_STREAM_KERNEL<T, NCAP, MCAP, true, true>), dim3(a.batch), dim3(64), 0, s, a, nc, mc, sa MPCQ_WAVE_REF_ARG(ref) MPCQ_WAVE_LOG_ARG(lg));
     else
-        hipLaunchKernelGGL((MPCQ_WAVE_STREAM_KERNEL<T, NCAP, MCAP, false, false>), dim3(a.batch), dim3(64), 0, s, a, nc, mc, sa MPCQ_WAVE_REF_ARG(ref));
+        hipLaunchKernelGGL((MPCQ_WAVE_STREAM_KERNEL<T, NCAP, MCAP, false, false>), dim3(a.batch), dim3(64), 0, s, a, nc, mc, sa MPCQ_WAVE_REF_ARG(ref) MPCQ_WAVE_LOG_ARG(lg));
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -692,7 +719,8 @@ static int wave_launch_any(const AdmmArgs<T> &a, int nc, int mc, int grid, hipSt
 }
 
 template <typename T>
-static int stream_launch_any(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa, hipStream_t s, const RefArgs *ref = nullptr)
+static int stream_launch_any(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa, hipStream_t s, const RefArgs *ref = nullptr,
+                             const LogArgs *lg = nullptr)
 {
     int best = -1, bn = 0, bm = 0;
 #define MPCQ_PICK(NC_, MC_)                                                  \
@@ -701,7 +729,7 @@ static int stream_launch_any(const AdmmArgs<T> &a, int nc, int mc, const StreamA
     }
     MPCQ_WAVE_CAPS(MPCQ_PICK)
 #undef MPCQ_PICK
-#define MPCQ_TRY(NC_, MC_) if (bn == NC_ && bm == MC_) return stream_launch<T, NC_, MC_>(a, nc, mc, sa, s, ref);
+#define MPCQ_TRY(NC_, MC_) if (bn == NC_ && bm == MC_) return stream_launch<T, NC_, MC_>(a, nc, mc, sa, s, ref, lg);
     MPCQ_WAVE_CAPS(MPCQ_TRY)
 #undef MPCQ_TRY
     return -1;
