@@ -221,6 +221,47 @@ int mpcq_mpc_step_ref_device(mpcq_ctx *ctx, const double *X_dev, double *U_dev, 
 /* Host-memory form (copies in/out, synchronises), as mpcq_mpc_step is to mpcq_mpc_step_device. */
 int mpcq_mpc_step_ref(mpcq_ctx *ctx, const double *X, double *U, const double *ref, long long ref_stride);
 
+/* ---- active-set sensitivities of the last solve (no OSQP counterpart) -----------
+ * How x* moves with the QP's data at the active set of the last solve's final iterate.  Per QP, with the
+ * active rows taken by the polish rule on the scaled iterate (lower-active when z^ - l^ < -y^, otherwise
+ * upper-active when u^ - z^ < y^; lower rows first, then upper rows), A_a those rows of A and
+ * K = [P, A_a'; A_a, 0] (P symmetrised from its upper triangle): for a cotangent g = dL/dx* (n entries),
+ * K [v; w] = [g; 0] and
+ *   gq = -v                                    (dL/dq, n entries)
+ *   gl[i] = w_k where row i is the k-th reduced row and lower-active, else 0   (dL/dl)
+ *   gu[i] = w_k where row i is upper-active, else 0                            (dL/du)
+ * the vector-Jacobian product of x*(q, l, u) at a fixed active set.  Solved on the device in fp64 whatever
+ * the context's dtype, in the scaled space, with settings.delta and settings.polish_refine_iter as the polish
+ * pass uses them; the contract is the solution of the unregularised system.  n_active: rows of the reduced
+ * system.  A QP that did not end MPCQ_SOLVED (or whose reduced system could not be factored) gets all-zero
+ * gradients and n_active = -1.  With settings.polish the active set is that of the polished iterate.
+ * g_dev: batch*n cotangents (device, fp64), or NULL for g = e_0 (the applied move x*[0]) in every QP.  The
+ * outputs are device arrays gq batch*n, gl batch*m, gu batch*m, n_active batch; each may be NULL, not all.
+ * Serves the last mpcq_solve / mpcq_mpc_step(_device) / mpcq_mpc_step_ref(_device) of shared-plant and
+ * per-plant contexts, every dtype and device path.  Read-only on the context: a call between two solves
+ * leaves the second solve bit-identical.  The kernel runs on `stream`, ordered after the context's last
+ * stream (an event; see mpcq_device_view above), and the context's next solve is ordered after it.
+ * MPCQ_ERR_ORDER: no solve since the last setup, data update, warm / cold start or reset; after
+ * mpcq_mpc_plants_step_device (no operators are kept); after a stream run (mpcq_mpc_run*_device).
+ * MPCQ_ERR_ARG: n > 32 or m > 64; a MIMO context; every output NULL; `stream` under graph capture (nothing
+ * is recorded into the capture).  A refused call writes nothing. */
+int mpcq_sensitivity_device(mpcq_ctx *ctx, const double *g_dev, double *gq_dev, double *gl_dev, double *gu_dev,
+                            int *n_active_dev, void *stream);
+/* Host-memory form (copies in/out, synchronises); the same arrays on the host. */
+int mpcq_sensitivity(mpcq_ctx *ctx, const double *g, double *gq, double *gl, double *gu, int *n_active);
+/* Step gains of the condensed-MPC front end: the gradient of the applied move x*[0] (g = e_0) with respect to
+ * the last step's X, previous U and horizon reference, by the chain rule through q = Fx X + Fu U + Fr ref and
+ * u = W0 + Sbar X + Ku U:
+ *   dX = Fx' gq + Sbar' gu (batch*nx),  dU = Fu' gq + Ku' gu (batch),  dref = Fr' gq (batch*n)
+ * from the context's operators (shared or per plant), fp64 sums in ascending row index: the explicit-MPC
+ * feedback gain at the current active set.  After a scalar-xref step the gain with respect to xref is the
+ * sum of dref's entries.  Outputs are device arrays; each may be NULL, not all.  As mpcq_sensitivity_device
+ * otherwise; also MPCQ_ERR_ARG when the context has no MPC operators (mpcq_mpc_set_operators). */
+int mpcq_mpc_step_gains_device(mpcq_ctx *ctx, double *dX_dev, double *dU_dev, double *dref_dev, int *n_active_dev,
+                               void *stream);
+/* Host-memory form (synchronises). */
+int mpcq_mpc_step_gains(mpcq_ctx *ctx, double *dX, double *dU, double *dref, int *n_active);
+
 /* ---- receding-horizon stream (BASELINE config 5; the solver.cpp loop, solver.cpp:43-74, with the
  * serial plant replaced by a simulated one) ----------------------------------------------------
  * Plant of every QP: X <- Ad X + Bd U + w,  w ~ N(0, noise_std^2 I) drawn from a counter-based

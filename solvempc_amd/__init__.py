@@ -64,6 +64,7 @@ class BatchSolver:
         self._ctx = ctx
         self.device = int(device)
         self.nx = 0
+        self.solve_count = 0  # bumped by every solving method (diff.mpc_solution's backward checks it)
 
     def close(self):
         ctx = getattr(self, "_ctx", None)
@@ -127,6 +128,7 @@ class BatchSolver:
 
     # -- solve (:102) and results (:105)
     def solve(self, stream: int | None = None) -> None:
+        self.solve_count += 1
         _capi.check(lib().mpcq_solve(self._ctx, C.c_void_p(stream or 0)), "mpcq_solve")
 
     def solution(self) -> np.ndarray:
@@ -146,6 +148,48 @@ class BatchSolver:
         _capi.check(lib().mpcq_get_info(self._ctx, st.ctypes.data_as(C.POINTER(C.c_int)),
                                         it.ctypes.data_as(C.POINTER(C.c_int)), _dp(rho)), "mpcq_get_info")
         return st, it, rho
+
+    # -- active-set sensitivities of the last solve (mpcq_sensitivity*, mpcq_mpc_step_gains*)
+    def sensitivity(self, g=None):
+        """(gq, gl, gu, n_active) of the last solve for the cotangent ``g`` = dL/dx of shape (batch, n), or None
+        for e_0 in every QP (the applied move x[0]): the vector-Jacobian product of x*(q, l, u) at the active set
+        of the solve's final iterate, gq = dL/dq (batch, n), gl = dL/dl and gu = dL/du (batch, m); n_active the
+        rows of the reduced system, -1 (and zero gradients) where the QP did not end SOLVED."""
+        gp = None
+        if g is not None:
+            g = _c64(g).reshape(self.batch, self.n)
+            gp = _dp(g)
+        gq = np.empty((self.batch, self.n))
+        gl, gu = np.empty((self.batch, self.m)), np.empty((self.batch, self.m))
+        na = np.empty(self.batch, dtype=np.int32)
+        _capi.check(lib().mpcq_sensitivity(self._ctx, gp, _dp(gq), _dp(gl), _dp(gu),
+                                           na.ctypes.data_as(C.POINTER(C.c_int))), "mpcq_sensitivity")
+        return gq, gl, gu, na
+
+    def sensitivity_device(self, g_ptr: int = 0, gq_ptr: int = 0, gl_ptr: int = 0, gu_ptr: int = 0,
+                           n_active_ptr: int = 0, stream: int | None = None) -> None:
+        """Same on device-resident buffers (fp64; n_active int32); g_ptr 0: g = e_0; any output may be 0, not all.
+        Asynchronous on ``stream``, ordered after the solver's last stream."""
+        ptrs = [C.c_void_p(p or 0) for p in (g_ptr, gq_ptr, gl_ptr, gu_ptr, n_active_ptr)]
+        _capi.check(lib().mpcq_sensitivity_device(self._ctx, *ptrs, C.c_void_p(stream or 0)),
+                    "mpcq_sensitivity_device")
+
+    def mpc_step_gains(self):
+        """(dX, dU, dref, n_active) of the last MPC step: the gradient of the applied move x[0] with respect to
+        the step's X (batch, nx), previous U (batch) and horizon reference (batch, n) at the current active set
+        (after a scalar-xref step the gain with respect to xref is dref.sum(axis=1))."""
+        dX, dU, dref = np.empty((self.batch, self.nx)), np.empty(self.batch), np.empty((self.batch, self.n))
+        na = np.empty(self.batch, dtype=np.int32)
+        _capi.check(lib().mpcq_mpc_step_gains(self._ctx, _dp(dX), _dp(dU), _dp(dref),
+                                              na.ctypes.data_as(C.POINTER(C.c_int))), "mpcq_mpc_step_gains")
+        return dX, dU, dref, na
+
+    def mpc_step_gains_device(self, dX_ptr: int = 0, dU_ptr: int = 0, dref_ptr: int = 0, n_active_ptr: int = 0,
+                              stream: int | None = None) -> None:
+        """Same on device-resident buffers; asynchronous on ``stream``."""
+        ptrs = [C.c_void_p(p or 0) for p in (dX_ptr, dU_ptr, dref_ptr, n_active_ptr)]
+        _capi.check(lib().mpcq_mpc_step_gains_device(self._ctx, *ptrs, C.c_void_p(stream or 0)),
+                    "mpcq_mpc_step_gains_device")
 
     def polish_info(self):
         """(status_polish, n_active, pri_res, dua_res) of the last solve (mpcq_get_polish_info): OSQP's
@@ -197,9 +241,12 @@ class BatchSolver:
                 _c64(Sbar).reshape(k, self.m, self.nx), _c64(Ku).reshape(k, self.m), _c64(W0).reshape(k, self.m)]
         _capi.check(lib().mpcq_mpc_set_operators(self._ctx, self.nx, *[_dp(a) for a in args]),
                     "mpcq_mpc_set_operators")
+        # (kept for solvempc_amd.diff, whose backward pass applies the front end's chain rule in torch)
+        self._mpc_ops = dict(zip(("Fx", "Fu", "Fr", "Sbar", "Ku"), args[:5]))
 
     def mpc_step(self, X, U, xref: float = 0.0) -> np.ndarray:
         """One receding-horizon step for every QP from host X (batch, nx), U (batch); returns new U."""
+        self.solve_count += 1
         X = _c64(X).reshape(self.batch, self.nx)
         U = _c64(U).reshape(self.batch).copy()
         _capi.check(lib().mpcq_mpc_step(self._ctx, _dp(X), _dp(U), float(xref)), "mpcq_mpc_step")
@@ -209,6 +256,7 @@ class BatchSolver:
     def mpc_step_ref(self, X, U, ref) -> np.ndarray:
         """mpc_step with a horizon reference: ``ref`` of shape (n,) is shared by the batch, (batch, n) is
         one per QP (q_b = Fx X_b + Fu U_b + Fr ref_b); returns new U."""
+        self.solve_count += 1
         X = _c64(X).reshape(self.batch, self.nx)
         U = _c64(U).reshape(self.batch).copy()
         ref = _c64(ref)
@@ -225,6 +273,7 @@ class BatchSolver:
                             stream: int | None = None) -> None:
         """Same on device-resident fp64 buffers: QP b reads ref[b * ref_stride + j], j < n (ref_stride 0: one
         shared n-vector); the buffer must stay unchanged until the solve has finished.  Asynchronous."""
+        self.solve_count += 1
         _capi.check(lib().mpcq_mpc_step_ref_device(self._ctx, C.c_void_p(X_ptr), C.c_void_p(U_ptr),
                                                    C.c_void_p(ref_ptr or 0), int(ref_stride),
                                                    C.c_void_p(stream or 0)), "mpcq_mpc_step_ref_device")
@@ -234,6 +283,7 @@ class BatchSolver:
                            stream: int) -> None:
         """mpc_run_device with a reference schedule: control step s = first_step + k of QP b uses
         ref[j] = sched[b * sched_stride + min(s + j, sched_len - 1)] (sched_stride 0: one shared schedule)."""
+        self.solve_count += 1
         _capi.check(lib().mpcq_mpc_run_ref_device(self._ctx, C.c_void_p(X_ptr), C.c_void_p(U_ptr),
                                                   C.c_void_p(sched_ptr or 0), int(sched_len), int(sched_stride),
                                                   int(steps), seed, first_qp, first_step, float(noise_std),
@@ -258,6 +308,7 @@ class BatchSolver:
         """``steps`` warm-started [controllerStep; plant update] rounds: one persistent launch on the
         one-QP-per-wave path (every wave runs its QP through all the steps), else replayed from a
         hipGraph."""
+        self.solve_count += 1
         _capi.check(lib().mpcq_mpc_run_device(self._ctx, C.c_void_p(X_ptr), C.c_void_p(U_ptr), float(xref),
                                               int(steps), seed, first_qp, first_step, float(noise_std),
                                               C.c_void_p(stream)), "mpcq_mpc_run_device")
@@ -345,6 +396,7 @@ class BatchSolver:
                                stream: int | None = None) -> None:
         """BASELINE config 3 in one pass: every plant's condensing + setup + one controllerStep (device
         pointers, plant-major fp64), operators kept on chip (the context keeps results only)."""
+        self.solve_count += 1
         ptrs = [C.c_void_p(p) for p in (Ad_ptr, Bd_ptr, Cd_ptr, K_ptr, Q_ptr, R_ptr, RD_ptr, X_ptr, U_ptr)]
         _capi.check(lib().mpcq_mpc_plants_step_device(self._ctx, int(nx), int(s_rows), *ptrs, float(xref),
                                                       C.c_void_p(stream or 0)), "mpcq_mpc_plants_step_device")
@@ -362,12 +414,14 @@ class BatchSolver:
 
     def mimo_step_device(self, X_ptr: int, U_ptr: int, yref_ptr: int = 0, stream: int | None = None) -> None:
         """One controllerStep for every QP on device-resident X (batch, nx), U (batch, nu); asynchronous."""
+        self.solve_count += 1
         _capi.check(lib().mpcq_mimo_step_device(self._ctx, C.c_void_p(X_ptr), C.c_void_p(U_ptr),
                                                 C.c_void_p(yref_ptr or 0), C.c_void_p(stream or 0)),
                     "mpcq_mimo_step_device")
 
     def mpc_step_device(self, X_ptr: int, U_ptr: int, xref: float = 0.0, stream: int | None = None) -> None:
         """Same on device-resident fp64 buffers (e.g. torch tensors' data_ptr()); asynchronous."""
+        self.solve_count += 1
         _capi.check(lib().mpcq_mpc_step_device(self._ctx, C.c_void_p(X_ptr), C.c_void_p(U_ptr),
                                                float(xref), C.c_void_p(stream or 0)), "mpcq_mpc_step_device")
 

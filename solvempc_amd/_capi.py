@@ -23,6 +23,7 @@ EXPORTS = (
     "mpcq_mimo_setup_plants_device", "mpcq_mimo_step_device", "mpcq_mpc_stream_counters",
     "mpcq_mpc_plants_step_device", "mpcq_get_stream_path", "mpcq_get_order", "mpcq_get_polish_info",
     "mpcq_mpc_step_ref_device", "mpcq_mpc_step_ref", "mpcq_mpc_run_ref_device", "mpcq_mpc_set_stream_log",
+    "mpcq_sensitivity_device", "mpcq_sensitivity", "mpcq_mpc_step_gains_device", "mpcq_mpc_step_gains",
 )
 
 
@@ -109,6 +110,10 @@ def lib() -> C.CDLL:
         "mpcq_mpc_step_ref": (C.c_int, [vp, dp, dp, dp, C.c_longlong]),
         "mpcq_mpc_run_ref_device": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_ulonglong,
                                               C.c_longlong, C.c_longlong, C.c_double, vp]),
+        "mpcq_sensitivity_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+        "mpcq_sensitivity": (C.c_int, [vp, dp, dp, dp, dp, ip]),
+        "mpcq_mpc_step_gains_device": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+        "mpcq_mpc_step_gains": (C.c_int, [vp, dp, dp, dp, ip]),
         "mpcq_mpc_set_plant": (C.c_int, [vp, C.c_int, dp, dp]),
         "mpcq_mpc_simulate_device": (C.c_int, [vp, vp, vp, C.c_ulonglong, C.c_longlong, C.c_longlong, C.c_double, vp]),
         "mpcq_mpc_run_device": (C.c_int, [vp, vp, vp, C.c_double, C.c_int, C.c_ulonglong, C.c_longlong,

@@ -193,6 +193,14 @@ struct mpcq_ctx {
     int *d_pol_status = nullptr, *d_pol_nact = nullptr;
     double *d_pol_res = nullptr;
     bool pol_valid = false;
+    // active-set sensitivities (mpcq_sens.hip).  sens_ok: the warm state and d_l, d_u are those of a solve that
+    // mpcq_sensitivity* serves (set by launch_solve outside a stream run; cleared by every setup, data update,
+    // warm / cold start, reset and stream run).  d_sens: staging of the host forms and the step gains' (gq, gu),
+    // allocated on first use (g, gq: batch*n; gl, gu: batch*m; dX: batch*8; dU: batch; dref: batch*n; then
+    // batch ints).  sens_ev orders a caller's stream after the context's last stream and back.
+    bool sens_ok = false;
+    double *d_sens = nullptr;
+    hipEvent_t sens_ev = nullptr;
     // host copies of plant-0 scaling
     std::vector<double> hD, hE;
     double hc = 1.0;
@@ -554,7 +562,8 @@ int mpcq_destroy(mpcq_ctx *c)
                     c->d_Sbar, c->d_Ku, c->d_W0, c->d_X, c->d_U, c->d_img, c->d_list, c->d_counts,
                     c->d_itstate, c->d_Ad, c->d_Bd, c->d_step, c->d_flags, c->d_stamps, c->d_mimo,
                     c->d_it_acc, c->d_uns_acc, c->d_Xs, c->d_Us, c->d_ordmap, c->d_ord, c->d_pol_status,
-                    c->d_pol_nact, c->d_pol_res, c->d_ref, c->d_ordG, c->d_logref};
+                    c->d_pol_nact, c->d_pol_res, c->d_ref, c->d_ordG, c->d_logref, c->d_sens};
+    if (c->sens_ev) (void)hipEventDestroy(c->sens_ev);
     if (c->gexec) (void)hipGraphExecDestroy(c->gexec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     for (void *p : ptrs)
@@ -697,6 +706,7 @@ int mpcq_setup(mpcq_ctx *c, const double *P, const double *q0, const double *A, 
         if (l0[i] > u0[i]) return fail(MPCQ_ERR_BOUNDS, "lower bound above upper bound (osqp validate_data)");
     if ((rc = ensure_plant_buffers(c))) return rc;
     c->mode = mpcq_ctx::Mode::None;
+    c->sens_ok = false;
     // rows n + j of A are the negated rows j (the reference's Gbar = [K0 L; -K0 L],
     // ModelPredictiveControlAPI.cpp:332-347), checked bit for bit: the tile kernel's paired loop
     c->paired = Pn == 1 && m == 2 * n && n % 4 == 0;
@@ -724,6 +734,7 @@ int mpcq_update_lin_cost(mpcq_ctx *c, const double *q)
     if (rc) return rc;
     if ((rc = materialize_qu(c))) return rc;  // (the other vector of the pending step)
     if (!q) return fail(MPCQ_ERR_ARG, "null q");
+    c->sens_ok = false;  // (d_q, d_l, d_u are no longer the last solve's)
     return h2d(c->d_q, q, 8 * (size_t)c->dims.batch * c->dims.n, c->last);
 }
 
@@ -733,6 +744,7 @@ int mpcq_update_upper_bound(mpcq_ctx *c, const double *u)
     if (rc) return rc;
     if ((rc = materialize_qu(c))) return rc;  // (the other vector of the pending step)
     if (!u) return fail(MPCQ_ERR_ARG, "null u");
+    c->sens_ok = false;
     return h2d(c->d_u, u, 8 * (size_t)c->dims.batch * c->dims.m, c->last);
 }
 
@@ -745,6 +757,7 @@ int mpcq_update_lower_bound(mpcq_ctx *c, const double *l)
     const bool lf = lower_all_free_batch(c, l);
     if (lf != c->lower_free) c->gen++;
     c->lower_free = lf;
+    c->sens_ok = false;
     return h2d(c->d_l, l, 8 * (size_t)c->dims.batch * c->dims.m, c->last);
 }
 
@@ -758,6 +771,7 @@ int mpcq_cold_start(mpcq_ctx *c)
 {
     int rc = check_ctx(c, kGeneric);
     if (rc) return rc;
+    c->sens_ok = false;  // (the warm state is no longer the last solve's iterate)
     if ((rc = reset_state(c, false))) return rc;
     HIPCHK(hipStreamSynchronize(c->last));
     return MPCQ_OK;
@@ -769,6 +783,7 @@ int mpcq_warm_start(mpcq_ctx *c, const double *x, const double *y)
     if (rc) return rc;
     if (!x || (c->dims.m && !y)) return fail(MPCQ_ERR_ARG, "null x/y");
     c->xy_lazy = false;  // (x, y are staged in the output buffers below; a rejected call keeps a pending x, y)
+    c->sens_ok = false;
     // stage in the output buffers (overwritten by the next solve)
     if ((rc = h2d(c->d_x, x, 8 * (size_t)c->dims.batch * c->dims.n, c->last))) return rc;
     if ((rc = h2d(c->d_y, y, 8 * (size_t)c->dims.batch * c->dims.m, c->last))) return rc;
@@ -1249,6 +1264,7 @@ static int launch_solve(mpcq_ctx *c, hipStream_t s, bool mpc, const double *X, d
     c->last = s;
     c->fresh = false;
     c->pol_valid = false;
+    c->sens_ok = !c->stream_acc;  // (a stream run's per-step solves are not served: mpcq_sensitivity_device)
     if (c->set.polish) {
         if (int prc = launch_polish(c, s, mpc ? U : nullptr)) return prc;
     }
@@ -1268,6 +1284,7 @@ int mpcq_reset(mpcq_ctx *c)
     int rc = check_ctx(c, kAnySetup);
     if (rc) return rc;
     c->fresh = true;
+    c->sens_ok = false;
     return MPCQ_OK;
 }
 
@@ -1630,6 +1647,7 @@ int mpcq_mpc_set_operators(mpcq_ctx *c, int nx, const double *Fx, const double *
     if ((rc = materialize_qu(c))) return rc;  // (with the operators the pending step used)
     if (!alloc_mpc_ops(c, nx)) return fail(MPCQ_ERR_HIP, "hipMalloc failed");
     c->nx = nx;
+    c->sens_ok = false;  // (the last step's q, u came from the operators being replaced)
     hipStream_t s = c->last;
     if ((rc = h2d(c->d_Fx, Fx, 8 * Pn * n * nx, s)) || (rc = h2d(c->d_Fu, Fu, 8 * Pn * n, s)) ||
         (rc = h2d(c->d_Fr, Fr, 8 * Pn * n * n, s)) || (rc = h2d(c->d_Sbar, Sbar, 8 * Pn * m * nx, s)) ||
@@ -1710,6 +1728,173 @@ int mpcq_mpc_step_ref(mpcq_ctx *c, const double *X, double *U, const double *ref
     RefScope scope(c, mpcq::RefArgs{c->d_ref, ref_stride ? (long long)n : 0, 0, nullptr, (int)n});
     if ((rc = launch_solve(c, c->last, true, c->d_X, c->d_U, 0.0))) return rc;
     return d2h(c, U, c->d_U, 8 * B);
+}
+
+// ---- active-set sensitivities of the last solve (mpcq_sens.hip; include/mpcq.h)
+namespace {
+
+// Staging block of the host forms and of the step gains' (gq, gu): offsets in doubles, the ints last
+struct SensStage {
+    size_t g, gq, gl, gu, dX, dU, dref, nact, total;
+    explicit SensStage(const mpcq_ctx *c)
+    {
+        const size_t B = c->dims.batch, n = c->dims.n, m = c->dims.m;
+        g = 0; gq = g + B * n; gl = gq + B * n; gu = gl + B * m; dX = gu + B * m; dU = dX + B * 8;
+        dref = dU + B; nact = dref + B * n; total = nact + (B + 1) / 2;
+    }
+};
+
+int sens_stage(mpcq_ctx *c)
+{
+    if (c->d_sens) return MPCQ_OK;
+    if (hipMalloc((void **)&c->d_sens, 8 * SensStage(c).total) != hipSuccess) {
+        c->d_sens = nullptr;
+        return fail(MPCQ_ERR_HIP, "hipMalloc failed (sensitivity staging)");
+    }
+    return MPCQ_OK;
+}
+
+// The refusals of include/mpcq.h, before anything is enqueued or written
+int sens_check(mpcq_ctx *c, const char *fn, bool gains, bool any_out, hipStream_t s)
+{
+    if (!c) return fail(MPCQ_ERR_ARG, "null context");
+    if (c->mimo_only || c->mode == mpcq_ctx::Mode::Mimo || c->dims.n > 32 || c->dims.m > 64)
+        return fail(MPCQ_ERR_ARG, std::string(fn) + ": serves n <= 32, m <= 64 and no MIMO context");
+    if (!any_out) return fail(MPCQ_ERR_ARG, std::string(fn) + ": every output is NULL");
+    int rc = check_ctx(c, kGeneric);
+    if (rc) return rc;
+    if (gains && !c->mpc_ready) return fail(MPCQ_ERR_ARG, std::string(fn) + ": the context has no MPC operators");
+    if (!c->sens_ok)
+        return fail(MPCQ_ERR_ORDER, std::string(fn) + ": needs a solve (mpcq_solve / mpcq_mpc_step*) as the context's "
+                                                      "last solver call; stream runs are not served");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return fail(MPCQ_ERR_ARG, std::string(fn) + ": the stream is under graph capture");
+    }
+    return MPCQ_OK;
+}
+
+// The kernels on s, ordered after the context's last stream; the context's next launches ordered after them.
+// Whatever the solve left lazy that the kernel reads (u of a tile-path controllerStep; status of an ordered
+// chain) is published first, on the context's last stream.  dX .. dref non-null: the step gains' chain rule on
+// (gq, gu), which are then staging buffers.
+int sens_enqueue(mpcq_ctx *c, const double *g, double *gq, double *gl, double *gu, int *nact, double *dX, double *dU,
+                 double *dref, bool chain, hipStream_t s)
+{
+    int rc = materialize_qu(c);
+    if (rc || (rc = materialize_info(c))) return rc;
+    if (s != c->last) {
+        if (!c->sens_ev) HIPCHK(hipEventCreateWithFlags(&c->sens_ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->sens_ev, c->last));
+        HIPCHK(hipStreamWaitEvent(s, c->sens_ev, 0));
+    }
+    mpcq::SensArgs a{};
+    a.batch = c->dims.batch;
+    a.n = c->dims.n;
+    a.m = c->dims.m;
+    a.nc = c->nc;
+    a.mc = c->mc;
+    a.shared = c->dims.n_plants == 1;
+    a.is_f32 = c->dims.dtype == MPCQ_F32;
+    a.ops_stride = c->ops_stride;
+    a.ops = c->d_ops;
+    a.P = c->d_P;
+    a.A = c->d_A;
+    a.l = c->d_l;
+    a.u = c->d_u;
+    a.zs = c->d_zs;
+    a.ys = c->d_ys;
+    a.status = c->d_status;
+    a.g = g;
+    a.gq = gq;
+    a.gl = gl;
+    a.gu = gu;
+    a.n_active = nact;
+    a.delta = c->set.delta;
+    a.refine = c->set.polish_refine_iter;
+    hipError_t err = hipSuccess;
+    const int src = mpcq_internal_sens_launch(&a, c->cus, s, &err);
+    if (src == -1) return fail(MPCQ_ERR_ARG, "sensitivity: the kernel serves n <= 32, m <= 64");
+    if (src) return fail(MPCQ_ERR_HIP, std::string("sensitivity kernel launch failed: ") + hipGetErrorString(err));
+    if (chain) {
+        mpcq::SensChainArgs ca{};
+        ca.batch = c->dims.batch;
+        ca.n = c->dims.n;
+        ca.m = c->dims.m;
+        ca.nx = c->nx;
+        ca.shared = c->dims.n_plants == 1;
+        ca.Fx = c->d_Fx;
+        ca.Fu = c->d_Fu;
+        ca.Fr = c->d_Fr;
+        ca.Sbar = c->d_Sbar;
+        ca.Ku = c->d_Ku;
+        ca.gq = gq;
+        ca.gu = gu;
+        ca.dX = dX;
+        ca.dU = dU;
+        ca.dref = dref;
+        if (mpcq_internal_sens_chain_launch(&ca, s)) return fail(MPCQ_ERR_HIP, "step-gain kernel launch failed");
+    }
+    if (s != c->last) {
+        HIPCHK(hipEventRecord(c->sens_ev, s));
+        HIPCHK(hipStreamWaitEvent(c->last, c->sens_ev, 0));
+    }
+    return MPCQ_OK;
+}
+
+}  // namespace
+
+int mpcq_sensitivity_device(mpcq_ctx *c, const double *g, double *gq, double *gl, double *gu, int *n_active,
+                            void *stream)
+{
+    int rc = sens_check(c, "mpcq_sensitivity_device", false, gq || gl || gu || n_active, (hipStream_t)stream);
+    if (rc) return rc;
+    return sens_enqueue(c, g, gq, gl, gu, n_active, nullptr, nullptr, nullptr, false, (hipStream_t)stream);
+}
+
+int mpcq_sensitivity(mpcq_ctx *c, const double *g, double *gq, double *gl, double *gu, int *n_active)
+{
+    int rc = sens_check(c, "mpcq_sensitivity", false, gq || gl || gu || n_active, c ? c->last : nullptr);
+    if (rc || (rc = sens_stage(c))) return rc;
+    const size_t B = c->dims.batch, n = c->dims.n, m = c->dims.m;
+    const SensStage o(c);
+    double *d = c->d_sens;
+    if (g && (rc = h2d(d + o.g, g, 8 * B * n, c->last))) return rc;
+    if ((rc = sens_enqueue(c, g ? d + o.g : nullptr, d + o.gq, d + o.gl, d + o.gu, (int *)(d + o.nact), nullptr, nullptr,
+                           nullptr, false, c->last)))
+        return rc;
+    if ((rc = d2h(c, gq, d + o.gq, 8 * B * n)) || (rc = d2h(c, gl, d + o.gl, 8 * B * m)) ||
+        (rc = d2h(c, gu, d + o.gu, 8 * B * m)) || (rc = d2h(c, n_active, d + o.nact, 4 * B)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(c->last));
+    return MPCQ_OK;
+}
+
+int mpcq_mpc_step_gains_device(mpcq_ctx *c, double *dX, double *dU, double *dref, int *n_active, void *stream)
+{
+    int rc = sens_check(c, "mpcq_mpc_step_gains_device", true, dX || dU || dref || n_active, (hipStream_t)stream);
+    if (rc || (rc = sens_stage(c))) return rc;
+    const SensStage o(c);
+    double *d = c->d_sens;
+    return sens_enqueue(c, nullptr, d + o.gq, nullptr, d + o.gu, n_active, dX, dU, dref, true, (hipStream_t)stream);
+}
+
+int mpcq_mpc_step_gains(mpcq_ctx *c, double *dX, double *dU, double *dref, int *n_active)
+{
+    int rc = sens_check(c, "mpcq_mpc_step_gains", true, dX || dU || dref || n_active, c ? c->last : nullptr);
+    if (rc || (rc = sens_stage(c))) return rc;
+    const size_t B = c->dims.batch, n = c->dims.n;
+    const SensStage o(c);
+    double *d = c->d_sens;
+    if ((rc = sens_enqueue(c, nullptr, d + o.gq, nullptr, d + o.gu, (int *)(d + o.nact), d + o.dX, d + o.dU, d + o.dref,
+                           true, c->last)))
+        return rc;
+    if ((rc = d2h(c, dX, d + o.dX, 8 * B * c->nx)) || (rc = d2h(c, dU, d + o.dU, 8 * B)) ||
+        (rc = d2h(c, dref, d + o.dref, 8 * B * n)) || (rc = d2h(c, n_active, d + o.nact, 4 * B)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(c->last));
+    return MPCQ_OK;
 }
 
 int mpcq_mpc_set_plant(mpcq_ctx *c, int nx, const double *Ad, const double *Bd)
@@ -1935,6 +2120,7 @@ static int mpc_run(mpcq_ctx *c, const char *fn, double *X, double *U, double xre
         explicit Acc(mpcq_ctx *cc) : c(cc) { c->stream_acc = true; }
         ~Acc() { c->stream_acc = false; }
     } acc(c);
+    c->sens_ok = false;  // (the warm state becomes the stream's last step's)
     if (mpcq_internal_set_step(c->d_step, first_step, s)) return fail(MPCQ_ERR_HIP, "set_step launch failed");
     const bool sync_each = debug_hook("MPCQ_DEBUG_SYNC")[0] == '1';  // synchronise every stage
     auto stage = [&](const char *what) -> int {
@@ -2147,6 +2333,7 @@ int mpcq_mpc_setup_plants_device(mpcq_ctx *c, int nx, int s_rows, const double *
     if (!alloc_mpc_ops(c, nx)) return fail(MPCQ_ERR_HIP, "hipMalloc failed");
     c->nx = nx;
     c->mode = mpcq_ctx::Mode::None;
+    c->sens_ok = false;
     hipStream_t s = (hipStream_t)stream;
     c->last = s;
     mpcq::CondenseArgs a{};
@@ -2301,6 +2488,7 @@ int mpcq_mpc_plants_step_device(mpcq_ctx *c, int nx, int s_rows, const double *A
     if (ordered) c->ord_clean = true;
     c->ord_last = ordered;
     c->mode = mpcq_ctx::Mode::OneShot;  // results only: no operator blocks were written
+    c->sens_ok = false;
     c->mpc_ready = false;
     c->last = s;
     return MPCQ_OK;
@@ -2331,6 +2519,7 @@ int mpcq_mimo_setup_plants_device(mpcq_ctx *c, int nx, int nu, int ny, int s_row
         return fail(MPCQ_ERR_HIP, "hipMalloc failed (mimo operator blocks)");
     c->mimo_N = N; c->mimo_nx = nx; c->mimo_nu = nu; c->mimo_ny = ny; c->mimo_srows = s_rows;
     c->mode = mpcq_ctx::Mode::None;
+    c->sens_ok = false;
     c->gen++;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(c->d_flags, 0, 4, s));

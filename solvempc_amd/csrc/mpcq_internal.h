@@ -457,6 +457,34 @@ struct PolishArgs {
     double delta;
     int refine, scaled_termination;
 };
+
+// Arguments of sens_kernel (mpcq_sens.hip): the active-set sensitivities of the last solve, one QP per wave,
+// fp64.  Everything of the context is read-only.
+struct SensArgs {
+    int batch, n, m, nc, mc;
+    int shared;                 // 1: every QP uses plant 0
+    int is_f32;                 // the warm state is float (MPCQ_F32 contexts), else double
+    size_t ops_stride;
+    const double *ops;          // [plant] OpsLayout(nc, mc): D, E, c
+    const double *P, *A;        // [plant] n*n (upper triangle read), m*n: the unscaled setup data
+    const double *l, *u;        // [batch] m, m: the last solve's unscaled bounds
+    const void *zs, *ys;        // warm state [batch][mc] x 2
+    const int *status;          // [batch] only MPCQ_SOLVED QPs get a sensitivity
+    const double *g;            // [batch] n: the cotangent dL/dx, or null: e_0 for every QP
+    double *gq, *gl, *gu;       // [batch] n, m, m: dL/dq, dL/dl, dL/du (each may be null)
+    int *n_active;              // [batch] rows of the reduced system, -1 where no sensitivity exists (or null)
+    double delta;
+    int refine;
+};
+
+// Arguments of sens_chain_kernel (mpcq_sens.hip): the MPC front end's chain rule on (gq, gu).
+struct SensChainArgs {
+    int batch, n, m, nx;
+    int shared;                          // 1: every QP uses plant 0's operators
+    const double *Fx, *Fu, *Fr, *Sbar, *Ku;  // [plant] n*nx, n, n*n, m*nx, m
+    const double *gq, *gu;               // [batch] n, m
+    double *dX, *dU, *dref;              // [batch] nx, 1, n (each may be null)
+};
 }  // namespace mpcq
 
 // Launchers (extern "C" so the host library links them without templates).
@@ -464,6 +492,10 @@ extern "C" {
 // OSQP polish of every SOLVED QP (mpcq_polish.hip; n <= 32, m <= 64): 0 launched, -1 unsupported shape,
 // -2 HIP error (*err).  cus: compute units of the device (grid size).
 int mpcq_internal_polish_launch(const mpcq::PolishArgs *a, int cus, hipStream_t s, hipError_t *err);
+// Active-set sensitivities of every SOLVED QP (mpcq_sens.hip; n <= 32, m <= 64), same return codes; and the MPC
+// chain rule of the step gains (0 launched, -2 HIP error).
+int mpcq_internal_sens_launch(const mpcq::SensArgs *a, int cus, hipStream_t s, hipError_t *err);
+int mpcq_internal_sens_chain_launch(const mpcq::SensChainArgs *a, hipStream_t s);
 int mpcq_internal_setup_launch(const mpcq::SetupArgs *args, hipStream_t stream);
 int mpcq_internal_setup_wave_launch(const mpcq::SetupArgs *args, hipStream_t stream);
 // Per-plant setup with the direct inverse M(rho)^-1 (mpcq_setup_wave.hip; n <= 32, m <= 64).
