@@ -249,6 +249,30 @@ int mpcq_sensitivity_device(mpcq_ctx *ctx, const double *g_dev, double *gq_dev, 
                             int *n_active_dev, void *stream);
 /* Host-memory form (copies in/out, synchronises); the same arrays on the host. */
 int mpcq_sensitivity(mpcq_ctx *ctx, const double *g, double *gq, double *gl, double *gu, int *n_active);
+/* The same call with the gradients with respect to the QP's matrices and the active sets.  With
+ * x, y the solution and dual the solve returned (mpcq_get_solution, mpcq_get_dual), y_a = y on the active rows
+ * and 0 elsewhere, and w = gl + gu:
+ *   gP = 1/2 (gq x' + x gq')    n*n, row-major, symmetric   (dL/dP)
+ *   gA = y_a gq' - w x'         m*n, row-major, zero on inactive rows   (dL/dA)
+ * gP is the gradient with respect to a symmetric P: a caller who parametrises only the upper triangle that
+ * mpcq_setup reads takes gP[i][j] + gP[j][i] for i < j (and gP[i][i] on the diagonal).
+ * A context with n_plants == batch gets one pair per QP (gP batch*n*n, gA batch*m*n; zeros where n_active = -1);
+ * a shared-plant context gets the sums over the batch (gP n*n, gA m*n).  QPs with n_active = -1 are left out of
+ * the sums (their x may be NaN; nothing of them is read).  The sums are formed in a fixed order that depends
+ * on the batch alone (chunks of 256 QPs, added in ascending order; no atomics): two calls give identical bits.
+ * active: batch*2 words; word 2b holds the lower-active rows of QP b as a bit mask (bit i: row i), word 2b + 1
+ * the upper-active rows; both 0 where n_active = -1.
+ * Each of the seven outputs may be NULL, not all.  With gP, gA and active all NULL the call is
+ * mpcq_sensitivity_device, bit for bit.  Preconditions, refusals, stream ordering and the read-only guarantee
+ * are those of mpcq_sensitivity_device; like mpcq_device_view_get the call may first publish the lazily kept
+ * x, y of a tile-path solve (on the context's last stream).  Whatever the contraction reads and the caller
+ * passed as NULL (gq, gl, gu, the masks, n_active) and the partial sums live in staging owned by the context. */
+int mpcq_sensitivity_data_device(mpcq_ctx *ctx, const double *g_dev, double *gq_dev, double *gl_dev, double *gu_dev,
+                                 double *gP_dev, double *gA_dev, unsigned long long *active_dev, int *n_active_dev,
+                                 void *stream);
+/* Host-memory form (copies in/out, synchronises); the same arrays on the host. */
+int mpcq_sensitivity_data(mpcq_ctx *ctx, const double *g, double *gq, double *gl, double *gu, double *gP, double *gA,
+                          unsigned long long *active, int *n_active);
 /* Step gains of the condensed-MPC front end: the gradient of the applied move x*[0] (g = e_0) with respect to
  * the last step's X, previous U and horizon reference, by the chain rule through q = Fx X + Fu U + Fr ref and
  * u = W0 + Sbar X + Ku U:

@@ -174,6 +174,37 @@ class BatchSolver:
         _capi.check(lib().mpcq_sensitivity_device(self._ctx, *ptrs, C.c_void_p(stream or 0)),
                     "mpcq_sensitivity_device")
 
+    def sensitivity_data(self, g=None):
+        """(gq, gl, gu, gP, gA, active, n_active) of the last solve (mpcq_sensitivity_data): ``sensitivity`` plus
+        the gradients with respect to the matrices, gP = 1/2 (gq x' + x gq') and gA = y_a gq' - (gl + gu) x' -- of
+        shape (batch, n, n) and (batch, m, n) for a per-plant solver, summed over the batch to (n, n) and (m, n) for
+        a shared plant -- and the active sets as bit masks, active[b] = (lower-active rows, upper-active rows) of
+        QP b (uint64; bit i: row i).  gP is the gradient with respect to a symmetric P; for the upper triangle
+        that ``setup`` reads take gP[i, j] + gP[j, i], i < j.  QPs with n_active = -1 contribute nothing."""
+        gp = None
+        if g is not None:
+            g = _c64(g).reshape(self.batch, self.n)
+            gp = _dp(g)
+        k = (self.batch,) if self.n_plants != 1 else ()
+        gq = np.empty((self.batch, self.n))
+        gl, gu = np.empty((self.batch, self.m)), np.empty((self.batch, self.m))
+        gP, gA = np.empty(k + (self.n, self.n)), np.empty(k + (self.m, self.n))
+        act = np.empty((self.batch, 2), dtype=np.uint64)
+        na = np.empty(self.batch, dtype=np.int32)
+        _capi.check(lib().mpcq_sensitivity_data(self._ctx, gp, _dp(gq), _dp(gl), _dp(gu), _dp(gP), _dp(gA),
+                                                act.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                                na.ctypes.data_as(C.POINTER(C.c_int))), "mpcq_sensitivity_data")
+        return gq, gl, gu, gP, gA, act, na
+
+    def sensitivity_data_device(self, g_ptr: int = 0, gq_ptr: int = 0, gl_ptr: int = 0, gu_ptr: int = 0,
+                                gP_ptr: int = 0, gA_ptr: int = 0, active_ptr: int = 0, n_active_ptr: int = 0,
+                                stream: int | None = None) -> None:
+        """Same on device-resident buffers (fp64; active uint64 (batch, 2); n_active int32); g_ptr 0: g = e_0; any
+        output may be 0, not all.  Asynchronous on ``stream``, ordered after the solver's last stream."""
+        ptrs = [C.c_void_p(p or 0) for p in (g_ptr, gq_ptr, gl_ptr, gu_ptr, gP_ptr, gA_ptr, active_ptr, n_active_ptr)]
+        _capi.check(lib().mpcq_sensitivity_data_device(self._ctx, *ptrs, C.c_void_p(stream or 0)),
+                    "mpcq_sensitivity_data_device")
+
     def mpc_step_gains(self):
         """(dX, dU, dref, n_active) of the last MPC step: the gradient of the applied move x[0] with respect to
         the step's X (batch, nx), previous U (batch) and horizon reference (batch, n) at the current active set

@@ -24,6 +24,7 @@ EXPORTS = (
     "mpcq_mpc_plants_step_device", "mpcq_get_stream_path", "mpcq_get_order", "mpcq_get_polish_info",
     "mpcq_mpc_step_ref_device", "mpcq_mpc_step_ref", "mpcq_mpc_run_ref_device", "mpcq_mpc_set_stream_log",
     "mpcq_sensitivity_device", "mpcq_sensitivity", "mpcq_mpc_step_gains_device", "mpcq_mpc_step_gains",
+    "mpcq_sensitivity_data_device", "mpcq_sensitivity_data",
 )
 
 
@@ -112,6 +113,8 @@ def lib() -> C.CDLL:
                                               C.c_longlong, C.c_longlong, C.c_double, vp]),
         "mpcq_sensitivity_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
         "mpcq_sensitivity": (C.c_int, [vp, dp, dp, dp, dp, ip]),
+        "mpcq_sensitivity_data_device": (C.c_int, [vp] * 10),
+        "mpcq_sensitivity_data": (C.c_int, [vp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_ulonglong), ip]),
         "mpcq_mpc_step_gains_device": (C.c_int, [vp, vp, vp, vp, vp, vp]),
         "mpcq_mpc_step_gains": (C.c_int, [vp, dp, dp, dp, ip]),
         "mpcq_mpc_set_plant": (C.c_int, [vp, C.c_int, dp, dp]),

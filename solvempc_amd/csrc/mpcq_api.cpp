@@ -201,6 +201,9 @@ struct mpcq_ctx {
     bool sens_ok = false;
     double *d_sens = nullptr;
     hipEvent_t sens_ev = nullptr;
+    // mpcq_sensitivity_data*: the shared plant's partial sums, then the host form's gP, gA (grown on demand)
+    double *d_sdata = nullptr;
+    size_t sdata_cap = 0;
     // host copies of plant-0 scaling
     std::vector<double> hD, hE;
     double hc = 1.0;
@@ -562,7 +565,7 @@ int mpcq_destroy(mpcq_ctx *c)
                     c->d_Sbar, c->d_Ku, c->d_W0, c->d_X, c->d_U, c->d_img, c->d_list, c->d_counts,
                     c->d_itstate, c->d_Ad, c->d_Bd, c->d_step, c->d_flags, c->d_stamps, c->d_mimo,
                     c->d_it_acc, c->d_uns_acc, c->d_Xs, c->d_Us, c->d_ordmap, c->d_ord, c->d_pol_status,
-                    c->d_pol_nact, c->d_pol_res, c->d_ref, c->d_ordG, c->d_logref, c->d_sens};
+                    c->d_pol_nact, c->d_pol_res, c->d_ref, c->d_ordG, c->d_logref, c->d_sens, c->d_sdata};
     if (c->sens_ev) (void)hipEventDestroy(c->sens_ev);
     if (c->gexec) (void)hipGraphExecDestroy(c->gexec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
@@ -1733,14 +1736,15 @@ int mpcq_mpc_step_ref(mpcq_ctx *c, const double *X, double *U, const double *ref
 // ---- active-set sensitivities of the last solve (mpcq_sens.hip; include/mpcq.h)
 namespace {
 
-// Staging block of the host forms and of the step gains' (gq, gu): offsets in doubles, the ints last
+// Staging block of the host forms, of the step gains' (gq, gu) and of what the data gradients read that the caller
+// did not ask for: offsets in doubles, the ints and then the active-set masks (2 words per QP) last
 struct SensStage {
-    size_t g, gq, gl, gu, dX, dU, dref, nact, total;
+    size_t g, gq, gl, gu, dX, dU, dref, nact, act, total;
     explicit SensStage(const mpcq_ctx *c)
     {
         const size_t B = c->dims.batch, n = c->dims.n, m = c->dims.m;
         g = 0; gq = g + B * n; gl = gq + B * n; gu = gl + B * m; dX = gu + B * m; dU = dX + B * 8;
-        dref = dU + B; nact = dref + B * n; total = nact + (B + 1) / 2;
+        dref = dU + B; nact = dref + B * n; act = nact + (B + 1) / 2; total = act + 2 * B;
     }
 };
 
@@ -1780,10 +1784,12 @@ int sens_check(mpcq_ctx *c, const char *fn, bool gains, bool any_out, hipStream_
 // chain) is published first, on the context's last stream.  dX .. dref non-null: the step gains' chain rule on
 // (gq, gu), which are then staging buffers.
 int sens_enqueue(mpcq_ctx *c, const double *g, double *gq, double *gl, double *gu, int *nact, double *dX, double *dU,
-                 double *dref, bool chain, hipStream_t s)
+                 double *dref, bool chain, hipStream_t s, unsigned long long *act = nullptr, double *gP = nullptr,
+                 double *gA = nullptr, double *part = nullptr)
 {
     int rc = materialize_qu(c);
     if (rc || (rc = materialize_info(c))) return rc;
+    if ((gP || gA) && (rc = materialize_xy(c))) return rc;  // (the data gradients read the solve's x, y)
     if (s != c->last) {
         if (!c->sens_ev) HIPCHK(hipEventCreateWithFlags(&c->sens_ev, hipEventDisableTiming));
         HIPCHK(hipEventRecord(c->sens_ev, c->last));
@@ -1813,6 +1819,7 @@ int sens_enqueue(mpcq_ctx *c, const double *g, double *gq, double *gl, double *g
     a.n_active = nact;
     a.delta = c->set.delta;
     a.refine = c->set.polish_refine_iter;
+    a.active = act;
     hipError_t err = hipSuccess;
     const int src = mpcq_internal_sens_launch(&a, c->cus, s, &err);
     if (src == -1) return fail(MPCQ_ERR_ARG, "sensitivity: the kernel serves n <= 32, m <= 64");
@@ -1835,6 +1842,24 @@ int sens_enqueue(mpcq_ctx *c, const double *g, double *gq, double *gl, double *g
         ca.dU = dU;
         ca.dref = dref;
         if (mpcq_internal_sens_chain_launch(&ca, s)) return fail(MPCQ_ERR_HIP, "step-gain kernel launch failed");
+    }
+    if (gP || gA) {
+        mpcq::SensDataArgs da{};
+        da.batch = c->dims.batch;
+        da.n = c->dims.n;
+        da.m = c->dims.m;
+        da.shared = c->dims.n_plants == 1;
+        da.gq = gq;
+        da.gl = gl;
+        da.gu = gu;
+        da.x = c->d_x;
+        da.y = c->d_y;
+        da.active = act;
+        da.n_active = nact;
+        da.part = part;
+        da.gP = gP;
+        da.gA = gA;
+        if (mpcq_internal_sens_data_launch(&da, s)) return fail(MPCQ_ERR_HIP, "data-gradient kernel launch failed");
     }
     if (s != c->last) {
         HIPCHK(hipEventRecord(c->sens_ev, s));
@@ -1866,6 +1891,80 @@ int mpcq_sensitivity(mpcq_ctx *c, const double *g, double *gq, double *gl, doubl
         return rc;
     if ((rc = d2h(c, gq, d + o.gq, 8 * B * n)) || (rc = d2h(c, gl, d + o.gl, 8 * B * m)) ||
         (rc = d2h(c, gu, d + o.gu, 8 * B * m)) || (rc = d2h(c, n_active, d + o.nact, 4 * B)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(c->last));
+    return MPCQ_OK;
+}
+
+namespace {
+
+// d_sdata with room for `doubles`
+int sens_data_room(mpcq_ctx *c, size_t doubles)
+{
+    if (doubles <= c->sdata_cap) return MPCQ_OK;
+    HIPCHK(hipStreamSynchronize(c->last));
+    if (c->d_sdata) (void)hipFree(c->d_sdata);
+    c->sdata_cap = 0;
+    if (hipMalloc((void **)&c->d_sdata, 8 * doubles) != hipSuccess) {
+        c->d_sdata = nullptr;
+        return fail(MPCQ_ERR_HIP, "hipMalloc failed (data-gradient staging)");
+    }
+    c->sdata_cap = doubles;
+    return MPCQ_OK;
+}
+
+// doubles of the shared plant's partial sums (0 for a per-plant context)
+size_t sens_partials(const mpcq_ctx *c)
+{
+    if (c->dims.n_plants != 1) return 0;
+    const size_t B = c->dims.batch, n = c->dims.n, m = c->dims.m;
+    return (B + mpcq::kSensChunk - 1) / mpcq::kSensChunk * (n * n + m * n);
+}
+
+}  // namespace
+
+int mpcq_sensitivity_data_device(mpcq_ctx *c, const double *g, double *gq, double *gl, double *gu, double *gP, double *gA,
+                                 unsigned long long *active, int *n_active, void *stream)
+{
+    int rc = sens_check(c, "mpcq_sensitivity_data_device", false, gq || gl || gu || gP || gA || active || n_active,
+                        (hipStream_t)stream);
+    if (rc) return rc;
+    double *part = nullptr;
+    if (gP || gA) {  // what the contraction reads and the caller did not ask for: the context's staging
+        if ((rc = sens_stage(c)) || (rc = sens_data_room(c, sens_partials(c)))) return rc;
+        const SensStage o(c);
+        double *d = c->d_sens;
+        if (!gq) gq = d + o.gq;
+        if (!gl) gl = d + o.gl;
+        if (!gu) gu = d + o.gu;
+        if (!n_active) n_active = (int *)(d + o.nact);
+        if (!active) active = (unsigned long long *)(d + o.act);
+        part = c->d_sdata;
+    }
+    return sens_enqueue(c, g, gq, gl, gu, n_active, nullptr, nullptr, nullptr, false, (hipStream_t)stream, active, gP, gA,
+                        part);
+}
+
+int mpcq_sensitivity_data(mpcq_ctx *c, const double *g, double *gq, double *gl, double *gu, double *gP, double *gA,
+                          unsigned long long *active, int *n_active)
+{
+    int rc = sens_check(c, "mpcq_sensitivity_data", false, gq || gl || gu || gP || gA || active || n_active,
+                        c ? c->last : nullptr);
+    if (rc || (rc = sens_stage(c))) return rc;
+    const size_t B = c->dims.batch, n = c->dims.n, m = c->dims.m;
+    const size_t k = c->dims.n_plants == 1 ? 1 : B, np = sens_partials(c);
+    if ((gP || gA) && (rc = sens_data_room(c, np + k * (n * n + m * n)))) return rc;
+    const SensStage o(c);
+    double *d = c->d_sens;
+    double *dP = gP ? c->d_sdata + np : nullptr, *dA = gA ? c->d_sdata + np + k * n * n : nullptr;
+    auto *dact = (unsigned long long *)(d + o.act);
+    if (g && (rc = h2d(d + o.g, g, 8 * B * n, c->last))) return rc;
+    if ((rc = sens_enqueue(c, g ? d + o.g : nullptr, d + o.gq, d + o.gl, d + o.gu, (int *)(d + o.nact), nullptr, nullptr,
+                           nullptr, false, c->last, dact, dP, dA, c->d_sdata)))
+        return rc;
+    if ((rc = d2h(c, gq, d + o.gq, 8 * B * n)) || (rc = d2h(c, gl, d + o.gl, 8 * B * m)) ||
+        (rc = d2h(c, gu, d + o.gu, 8 * B * m)) || (rc = d2h(c, n_active, d + o.nact, 4 * B)) ||
+        (rc = d2h(c, active, dact, 16 * B)) || (rc = d2h(c, gP, dP, 8 * k * n * n)) || (rc = d2h(c, gA, dA, 8 * k * m * n)))
         return rc;
     HIPCHK(hipStreamSynchronize(c->last));
     return MPCQ_OK;

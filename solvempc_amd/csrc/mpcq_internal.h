@@ -475,6 +475,22 @@ struct SensArgs {
     int *n_active;              // [batch] rows of the reduced system, -1 where no sensitivity exists (or null)
     double delta;
     int refine;
+    unsigned long long *active; // [batch][2] lower-active, upper-active row bit masks; zeros where n_active = -1 (or null)
+};
+
+// Arguments of the data-gradient kernels (mpcq_sensdata.hip): gP, gA from a sens_kernel's outputs and the solve's
+// x, y.  A QP with n_active < 0 is skipped (none of its arrays is read).  shared: the sums over the batch, by
+// sens_contract_kernel (one partial of n*n + m*n doubles per kSensChunk QPs) and sens_reduce_kernel.
+constexpr int kSensChunk = 256;
+struct SensDataArgs {
+    int batch, n, m;
+    int shared;                          // 1: gP n*n, gA m*n summed over the batch; 0: one pair per QP
+    const double *gq, *gl, *gu;          // [batch] n, m, m
+    const double *x, *y;                 // [batch] n, m: the solve's solution and dual
+    const unsigned long long *active;    // [batch][2]
+    const int *n_active;                 // [batch]
+    double *part;                        // [ceil(batch / kSensChunk)][n*n + m*n] (shared plant)
+    double *gP, *gA;                     // each may be null
 };
 
 // Arguments of sens_chain_kernel (mpcq_sens.hip): the MPC front end's chain rule on (gq, gu).
@@ -496,6 +512,8 @@ int mpcq_internal_polish_launch(const mpcq::PolishArgs *a, int cus, hipStream_t 
 // chain rule of the step gains (0 launched, -2 HIP error).
 int mpcq_internal_sens_launch(const mpcq::SensArgs *a, int cus, hipStream_t s, hipError_t *err);
 int mpcq_internal_sens_chain_launch(const mpcq::SensChainArgs *a, hipStream_t s);
+// gP, gA of a sensitivity call (mpcq_sensdata.hip; n <= 32, m <= 64): 0 launched, -1 unsupported shape, -2 HIP error.
+int mpcq_internal_sens_data_launch(const mpcq::SensDataArgs *a, hipStream_t s);
 int mpcq_internal_setup_launch(const mpcq::SetupArgs *args, hipStream_t stream);
 int mpcq_internal_setup_wave_launch(const mpcq::SetupArgs *args, hipStream_t stream);
 // Per-plant setup with the direct inverse M(rho)^-1 (mpcq_setup_wave.hip; n <= 32, m <= 64).

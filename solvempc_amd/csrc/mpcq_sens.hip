@@ -60,6 +60,7 @@ __global__ __launch_bounds__(64) void sens_kernel(SensArgs a)
         const double *ops = a.ops + pp * a.ops_stride;
         int mr = 0, pos = 0;
         bool low = false, upp = false;
+        unsigned long long mlow = 0ull, mupp = 0ull;
         double sx = 0.0, sn = 0.0;
         if (ok) {
             const double c = ops[L.cs];
@@ -113,7 +114,8 @@ __global__ __launch_bounds__(64) void sens_kernel(SensArgs a)
             const double yh = lm ? state(a.ys, (size_t)b * mc + lane) : 0.0;
             low = lm && (zh - lo < -yh);
             upp = lm && !low && (up - zh < yh);
-            const unsigned long long mlow = __ballot(low), mupp = __ballot(upp);
+            mlow = __ballot(low);
+            mupp = __ballot(upp);
             const unsigned long long below = (1ull << lane) - 1ull;
             const int n_low = __popcll(mlow);
             mr = n_low + __popcll(mupp);
@@ -209,6 +211,7 @@ __global__ __launch_bounds__(64) void sens_kernel(SensArgs a)
         if (lm && a.gl) a.gl[(size_t)b * m + lane] = low ? wv : 0.0;
         if (lm && a.gu) a.gu[(size_t)b * m + lane] = upp ? wv : 0.0;
         if (lane == 0 && a.n_active) a.n_active[b] = ok ? mr : -1;
+        if (lane < 2 && a.active) a.active[2 * (size_t)b + lane] = ok ? (lane ? mupp : mlow) : 0ull;
     }
 }
 
