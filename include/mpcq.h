@@ -373,6 +373,39 @@ int mpcq_condense(int device, int n_plants, int nx, int N, int s_rows, const dou
                   const double *R, const double *RD, double *P, double *A, double *Fx, double *Fu,
                   double *Fr, double *Sbar, double *Ku, double *W0);
 
+/* Reverse of mpcq_condense: cotangents of the condensed operators -> cotangents of the plant
+ * data, the vector-Jacobian product of the condensing.  All pointers are device pointers, fp64, plant-major
+ * (n_plants copies); Ad .. RD as mpcq_condense reads them, gP .. gKu of the shapes of its outputs P, A, Fx, Fu, Fr,
+ * Sbar, Ku (each may be NULL = 0, not all), gAd .. gRD of the shapes of Ad .. RD (each may be NULL, not all).
+ * With L the lower-triangular ones, r_k = Cd Ad^k, S(i,j) = sum_(k <= i-j) r_k Bd for j <= i (else 0) and
+ * Sx(i) = r_(i+1) as the condensing forms them, and Ps = gP + gP':
+ *   gR  = <Ps, L'L> + 2 sum gFu             gRD = tr Ps
+ *   gQ  = <Ps, S'S> + 2 gFu.(S(:,0)'S) - 2 <gFr, S'> + 2 <gFx, S'Sx>
+ *   GS  = 2Q S Ps + 2Q S(:,0) gFu' - 2Q gFr' + 2Q Sx gFx',  GS(:,0) += 2Q S gFu     (its lower triangle is used)
+ *   GSx = 2Q S gFx
+ *   Gc_d = sum_(i-j = d) GS(i,j),  GCAB_k = sum_(d >= k) Gc_d,  gBd = sum_(k < N) GCAB_k r_k'
+ *   rho_k = GCAB_k Bd' (k < N) + GSx(k-1) (k >= 1);  for k = N .. 1:  gAd += r_(k-1)' rho_k,
+ *   rho_(k-1) += rho_k Ad';  gCd = rho_0
+ *   gK[c] = sum_(i < min(s_rows, N)) (gSbar(i,c) - gSbar(N+i,c));  gK[0] also receives
+ *   sum_(j <= i) (gA(i,j) - gA(N+i,j)) - sum_(i < N) gKu[i] + sum_(i < N) gKu[N+i]
+ * W0 is constant and has no cotangent.  gP is the cotangent of the full symmetric P that mpcq_condense writes
+ * (the convention of mpcq_sensitivity_data's gP).  Stateless: no context is touched.  One wavefront per plant,
+ * fp64, no atomics, sums in a fixed order: two calls give identical bits, and the outputs asked for do not
+ * depend on which others are NULL.  The kernel runs on `stream` of device `device`.
+ * MPCQ_ERR_ARG, with nothing written: N < 1 or N > 32, nx < 1 or nx > 8, s_rows < 0, n_plants < 1; a NULL plant
+ * array; every cotangent NULL or every output NULL; `stream` under graph capture. */
+int mpcq_condense_vjp_device(int device, int n_plants, int nx, int N, int s_rows, const double *Ad, const double *Bd,
+                             const double *Cd, const double *K, const double *Q, const double *R, const double *RD,
+                             const double *gP, const double *gA, const double *gFx, const double *gFu,
+                             const double *gFr, const double *gSbar, const double *gKu, double *gAd, double *gBd,
+                             double *gCd, double *gK, double *gQ, double *gR, double *gRD, void *stream);
+/* Host-memory form (copies in/out, synchronises); the same arrays on the host. */
+int mpcq_condense_vjp(int device, int n_plants, int nx, int N, int s_rows, const double *Ad, const double *Bd,
+                      const double *Cd, const double *K, const double *Q, const double *R, const double *RD,
+                      const double *gP, const double *gA, const double *gFx, const double *gFu, const double *gFr,
+                      const double *gSbar, const double *gKu, double *gAd, double *gBd, double *gCd, double *gK,
+                      double *gQ, double *gR, double *gRD);
+
 /* Per-plant condensing + setup on the device (BASELINE config 3): every plant of the context
  * (n_plants copies, device pointers, plant-major: Ad nx*nx, Bd nx, Cd nx, K nx, Q, R, RD) is
  * condensed as mpcq_condense does, its front-end operators installed (as mpcq_mpc_set_operators)

@@ -457,4 +457,4 @@ class BatchSolver:
                                                float(xref), C.c_void_p(stream or 0)), "mpcq_mpc_step_device")
 
 
-from .mpc import ModelPredictiveControlAPI, from_json  # noqa: E402,F401
+from .mpc import ModelPredictiveControlAPI, condense, condense_vjp, condense_vjp_device, from_json  # noqa: E402,F401

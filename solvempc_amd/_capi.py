@@ -24,7 +24,7 @@ EXPORTS = (
     "mpcq_mpc_plants_step_device", "mpcq_get_stream_path", "mpcq_get_order", "mpcq_get_polish_info",
     "mpcq_mpc_step_ref_device", "mpcq_mpc_step_ref", "mpcq_mpc_run_ref_device", "mpcq_mpc_set_stream_log",
     "mpcq_sensitivity_device", "mpcq_sensitivity", "mpcq_mpc_step_gains_device", "mpcq_mpc_step_gains",
-    "mpcq_sensitivity_data_device", "mpcq_sensitivity_data",
+    "mpcq_sensitivity_data_device", "mpcq_sensitivity_data", "mpcq_condense_vjp_device", "mpcq_condense_vjp",
 )
 
 
@@ -125,6 +125,8 @@ def lib() -> C.CDLL:
         "mpcq_mpc_set_stream_log": (C.c_int, [vp, C.POINTER(StreamLog)]),
         "mpcq_mpc_plants_step_device": (C.c_int, [vp, C.c_int, C.c_int] + [vp] * 9 + [C.c_double, vp]),
         "mpcq_condense": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [dp] * 15),
+        "mpcq_condense_vjp_device": (C.c_int, [C.c_int] * 5 + [vp] * 21 + [vp]),
+        "mpcq_condense_vjp": (C.c_int, [C.c_int] * 5 + [dp] * 21),
         "mpcq_mpc_setup_plants_device": (C.c_int, [vp, C.c_int, C.c_int] + [vp] * 7 + [vp]),
         "mpcq_last_error": (C.c_char_p, []),
     }

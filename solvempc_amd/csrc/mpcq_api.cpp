@@ -2416,6 +2416,130 @@ int mpcq_condense(int device, int n_plants, int nx, int N, int s_rows, const dou
     return rc;
 }
 
+namespace {
+
+// The argument refusals of mpcq_condense_vjp* (include/mpcq.h), before anything is enqueued or written
+int condense_vjp_check(int n_plants, int nx, int N, int s_rows, const double *const (&plant)[7],
+                       const double *const (&cot)[7], double *const (&out)[7])
+{
+    if (n_plants < 1 || nx < 1 || nx > 8 || N < 1 || N > 32 || s_rows < 0)
+        return fail(MPCQ_ERR_ARG, "condense_vjp: n_plants >= 1, 1 <= nx <= 8, 1 <= N <= 32, s_rows >= 0");
+    bool any_cot = false, any_out = false;
+    for (auto p : plant)
+        if (!p) return fail(MPCQ_ERR_ARG, "condense_vjp: null plant array");
+    for (auto p : cot) any_cot |= p != nullptr;
+    for (auto p : out) any_out |= p != nullptr;
+    if (!any_cot) return fail(MPCQ_ERR_ARG, "condense_vjp: every cotangent is NULL");
+    if (!any_out) return fail(MPCQ_ERR_ARG, "condense_vjp: every output is NULL");
+    return MPCQ_OK;
+}
+
+int condense_vjp_launch(int n_plants, int nx, int N, int s_rows, const double *const (&plant)[7],
+                        const double *const (&cot)[7], double *const (&out)[7], hipStream_t s)
+{
+    mpcq::CondenseVjpArgs a{};
+    a.n_plants = n_plants;
+    a.nx = nx;
+    a.N = N;
+    a.s_rows = s_rows;
+    a.Ad = plant[0]; a.Bd = plant[1]; a.Cd = plant[2]; a.K = plant[3]; a.Q = plant[4]; a.R = plant[5]; a.RD = plant[6];
+    a.gP = cot[0]; a.gA = cot[1]; a.gFx = cot[2]; a.gFu = cot[3]; a.gFr = cot[4]; a.gSbar = cot[5]; a.gKu = cot[6];
+    a.gAd = out[0]; a.gBd = out[1]; a.gCd = out[2]; a.gK = out[3]; a.gQ = out[4]; a.gR = out[5]; a.gRD = out[6];
+    if (mpcq_internal_condense_vjp_launch(&a, s) != 0) return fail(MPCQ_ERR_HIP, "condense_vjp launch failed");
+    return MPCQ_OK;
+}
+
+// hipSetDevice(device) for the length of a stateless call; the caller's current device is put back afterwards
+struct DeviceScope {
+    int prev = -1, rc = MPCQ_OK;
+    explicit DeviceScope(int device)
+    {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+            (void)hipGetLastError();
+            rc = fail(MPCQ_ERR_HIP, "no HIP device with this ordinal");
+            return;
+        }
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess || (cur != device && hipSetDevice(device) != hipSuccess))
+            rc = fail(MPCQ_ERR_HIP, "hipSetDevice failed");
+        else if (cur != device)
+            prev = cur;
+    }
+    ~DeviceScope()
+    {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+}  // namespace
+
+int mpcq_condense_vjp_device(int device, int n_plants, int nx, int N, int s_rows, const double *Ad, const double *Bd,
+                             const double *Cd, const double *K, const double *Q, const double *R, const double *RD,
+                             const double *gP, const double *gA, const double *gFx, const double *gFu,
+                             const double *gFr, const double *gSbar, const double *gKu, double *gAd, double *gBd,
+                             double *gCd, double *gK, double *gQ, double *gR, double *gRD, void *stream)
+{
+    const double *const plant[7] = {Ad, Bd, Cd, K, Q, R, RD}, *const cot[7] = {gP, gA, gFx, gFu, gFr, gSbar, gKu};
+    double *const out[7] = {gAd, gBd, gCd, gK, gQ, gR, gRD};
+    int rc = condense_vjp_check(n_plants, nx, N, s_rows, plant, cot, out);
+    if (rc) return rc;
+    DeviceScope dev(device);
+    if (dev.rc) return dev.rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return fail(MPCQ_ERR_ARG, "mpcq_condense_vjp_device: the stream is under graph capture");
+    }
+    return condense_vjp_launch(n_plants, nx, N, s_rows, plant, cot, out, s);
+}
+
+int mpcq_condense_vjp(int device, int n_plants, int nx, int N, int s_rows, const double *Ad, const double *Bd,
+                      const double *Cd, const double *K, const double *Q, const double *R, const double *RD,
+                      const double *gP, const double *gA, const double *gFx, const double *gFu, const double *gFr,
+                      const double *gSbar, const double *gKu, double *gAd, double *gBd, double *gCd, double *gK,
+                      double *gQ, double *gR, double *gRD)
+{
+    const double *const plant[7] = {Ad, Bd, Cd, K, Q, R, RD}, *const cot[7] = {gP, gA, gFx, gFu, gFr, gSbar, gKu};
+    double *const out[7] = {gAd, gBd, gCd, gK, gQ, gR, gRD};
+    int rc = condense_vjp_check(n_plants, nx, N, s_rows, plant, cot, out);
+    if (rc) return rc;
+    DeviceScope dev(device);
+    if (dev.rc) return dev.rc;
+    const size_t Pn = n_plants, X = nx, n = N;
+    const size_t plant_cnt[7] = {Pn * X * X, Pn * X, Pn * X, Pn * X, Pn, Pn, Pn};
+    const size_t cot_cnt[7] = {Pn * n * n, Pn * 2 * n * n, Pn * n * X, Pn * n, Pn * n * n, Pn * 2 * n * X, Pn * 2 * n};
+    size_t total = 0;
+    for (int i = 0; i < 7; i++) total += 2 * plant_cnt[i] + (cot[i] ? cot_cnt[i] : 0);
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, 8 * total));
+    const double *dplant[7], *dcot[7];
+    double *dout[7], *p = buf;
+    for (int i = 0; i < 7 && !rc; i++) {
+        dplant[i] = p;
+        if (hipMemcpy(p, plant[i], 8 * plant_cnt[i], hipMemcpyHostToDevice) != hipSuccess) rc = fail(MPCQ_ERR_HIP, "h2d");
+        p += plant_cnt[i];
+    }
+    for (int i = 0; i < 7 && !rc; i++) {
+        dcot[i] = cot[i] ? p : nullptr;
+        if (!cot[i]) continue;
+        if (hipMemcpy(p, cot[i], 8 * cot_cnt[i], hipMemcpyHostToDevice) != hipSuccess) rc = fail(MPCQ_ERR_HIP, "h2d");
+        p += cot_cnt[i];
+    }
+    for (int i = 0; i < 7; i++) {
+        dout[i] = out[i] ? p : nullptr;
+        p += plant_cnt[i];
+    }
+    if (!rc) rc = condense_vjp_launch(n_plants, nx, N, s_rows, dplant, dcot, dout, nullptr);
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MPCQ_ERR_HIP, "condense_vjp kernel failed");
+    for (int i = 0; i < 7 && !rc; i++)
+        if (out[i] && hipMemcpy(out[i], dout[i], 8 * plant_cnt[i], hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(MPCQ_ERR_HIP, "d2h");
+    (void)hipFree(buf);
+    return rc;
+}
+
 
 int mpcq_mpc_setup_plants_device(mpcq_ctx *c, int nx, int s_rows, const double *Ad, const double *Bd,
                                  const double *Cd, const double *K, const double *Q, const double *R,

@@ -348,6 +348,13 @@ struct CondenseArgs {
     double *q0, *l0, *u0;                            // optional: the ctor's setup data (0, -DBL_MAX, W0)
     int force_ref;                                   // test hook: the workgroup kernel at any N
 };
+// The reverse of the condensing (mpcq_condense_vjp.hip): N <= 32, nx <= 8, one wavefront per plant.
+struct CondenseVjpArgs {
+    int n_plants, nx, N, s_rows;
+    const double *Ad, *Bd, *Cd, *K, *Q, *R, *RD;          // the plant data, as CondenseArgs
+    const double *gP, *gA, *gFx, *gFu, *gFr, *gSbar, *gKu;  // cotangents, shapes of CondenseArgs' outputs; null: 0
+    double *gAd, *gBd, *gCd, *gK, *gQ, *gR, *gRD;         // shapes of the plant data; each may be null
+};
 }  // namespace mpcq
 
 namespace mpcq {
@@ -525,6 +532,8 @@ int mpcq_internal_fill(void *p, int is_f32, double v, size_t count, hipStream_t 
 int mpcq_internal_caps(int n, int m, int *nc, int *mc);
 int mpcq_internal_condense_launch(const mpcq::CondenseArgs *a, hipStream_t s);
 size_t mpcq_internal_condense_scratch(int nx, int N);
+// 0 launched, -1 a shape the kernel does not serve (N > 32, nx > 8), -2 the launch failed.
+int mpcq_internal_condense_vjp_launch(const mpcq::CondenseVjpArgs *a, hipStream_t s);
 int mpcq_internal_admm_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, hipStream_t s);
 int mpcq_internal_admm_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, hipStream_t s);
 // The REF variants of the launchers (mpcq_*_ref_*.hip: the same kernels compiled with a per-QP horizon

@@ -10,12 +10,17 @@ did not end SOLVED.
 ``qp_solution`` is the QP itself as a layer: x*(P, A, q, l, u), with the gradients with respect to the matrices
 from ``BatchSolver.sensitivity_data_device`` (solvempc_amd/csrc/mpcq_sensdata.hip).  Gradients with
 respect to the front end's operators follow from it by autograd when q and u are formed from operator tensors in
-torch; gradients through the condensing to the plant's Ad, Bd, Q, R are out of scope."""
+torch.
+
+``mpc_plant_solution`` is the MPC step as a function of the plant model and the cost weights themselves: the
+condensing and the setup run on the device from the plant tensors (``BatchSolver.mpc_setup_plants_device``), and
+the backward pass chains ``sensitivity_data_device`` with the condensing's vector-Jacobian product
+(``solvempc_amd.condense_vjp_device``, solvempc_amd/csrc/mpcq_condense_vjp.hip)."""
 from __future__ import annotations
 
 import torch
 
-__all__ = ["mpc_solution", "qp_solution"]
+__all__ = ["mpc_solution", "qp_solution", "mpc_plant_solution"]
 
 
 class _DevArray:
@@ -117,6 +122,106 @@ class _QpSolution(torch.autograd.Function):
         solver.sensitivity_data_device(g.data_ptr(), gq.data_ptr(), gl.data_ptr(), gu.data_ptr(), gP.data_ptr(),
                                        gA.data_ptr(), 0, 0, stream)
         return None, gP, gA, gq, gl, gu, None
+
+
+_PLANT = ("Ad", "Bd", "Cd", "K", "Q", "R", "RD")
+
+
+class _MpcPlantSolution(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, s_rows, setup, Ad, Bd, Cd, K, Q, R, RD, X, U, ref):
+        from .mpc import condense
+        B, n, m, kp = solver.batch, solver.n, solver.m, solver.n_plants
+        if kp not in (1, B):
+            raise ValueError("mpc_plant_solution: the solver must have n_plants == 1 or n_plants == batch")
+        if m != 2 * n or n > 32:
+            raise ValueError("mpc_plant_solution: the solver must have m == 2 n and n <= 32 (the condensed-MPC shape)")
+        nx = int(Ad.shape[-1]) if Ad.dim() == 3 else 0
+        shapes = {"Ad": (kp, nx, nx), "Bd": (kp, nx), "Cd": (kp, nx), "K": (kp, nx), "Q": (kp,), "R": (kp,),
+                  "RD": (kp,), "X": (B, nx), "U": (B,), "ref": (B, n)}
+        given = dict(zip(_PLANT + ("X", "U", "ref"), (Ad, Bd, Cd, K, Q, R, RD, X, U, ref)))
+        for name, t in given.items():
+            if not (t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == shapes[name]):
+                raise ValueError(f"mpc_plant_solution: {name} must be a device fp64 tensor of shape {shapes[name]}")
+        plant = [given[k].detach().contiguous() for k in _PLANT]
+        Xc, U0, rc = X.detach().contiguous(), U.detach().contiguous(), ref.detach().contiguous()
+        Uc = U0.clone()  # (the step adds the applied move to its U)
+        stream = torch.cuda.current_stream(X.device).cuda_stream
+        if setup:
+            solver.mpc_setup_plants_device(nx, int(s_rows), *[t.data_ptr() for t in plant], stream)
+        elif solver.nx != nx:
+            raise ValueError(f"mpc_plant_solution: setup=False, but the solver holds plants of nx = {solver.nx}")
+        solver.mpc_step_ref_device(Xc.data_ptr(), Uc.data_ptr(), rc.data_ptr(), n, stream)
+        view = solver.device_view()  # (publishes x and status on the same stream)
+        x = torch.as_tensor(_DevArray(view["x"], (B, n), "<f8"), device=X.device).clone()
+        status = torch.as_tensor(_DevArray(view["status"], (B,), "<i4"), device=X.device).clone()
+        ctx.ops = None
+        if X.requires_grad or U.requires_grad or ref.requires_grad:  # (the chain rule of mpc_solution: via the host)
+            host = condense({k: t.cpu().numpy() for k, t in zip(_PLANT, plant)}, n, int(s_rows), solver.device)
+            ctx.ops = {k: torch.from_numpy(host[k]).to(X.device) for k in ("Fx", "Fu", "Fr", "Sbar", "Ku")}
+        # (Xc, rc stay alive until the solve has finished: later phases of a tile solve re-form q from them)
+        ctx.keep = (plant, Xc, U0, rc, Uc)
+        ctx.solver, ctx.count, ctx.dims = solver, solver.solve_count, (nx, int(s_rows))
+        ctx.mark_non_differentiable(status)
+        return x, status
+
+    @staticmethod
+    def backward(ctx, gx, _gstatus):
+        from .mpc import condense_vjp_device
+        solver = ctx.solver
+        if solver.solve_count != ctx.count:
+            raise RuntimeError("mpc_plant_solution.backward: the solver has solved again since this forward pass, so "
+                               "its state is no longer this solve's; run backward before the next solve")
+        B, n, m, kp = solver.batch, solver.n, solver.m, solver.n_plants
+        (nx, s_rows), (plant, X, U, ref, _) = ctx.dims, ctx.keep
+        g = gx.contiguous()
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=g.device)
+        gq, gu, gP, gA = new(B, n), new(B, m), new(kp, n, n), new(kp, m, n)
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        solver.sensitivity_data_device(g.data_ptr(), gq.data_ptr(), 0, gu.data_ptr(), gP.data_ptr(), gA.data_ptr(), 0, 0,
+                                       stream)
+        grads = [None] * 7
+        if any(ctx.needs_input_grad[3:10]):
+            # cotangents of the front end's operators: q = Fx X + Fu U + Fr ref, u = W0 + Sbar X + Ku U
+            if kp == 1:
+                cots = [gP, gA, gq.t() @ X, gq.t() @ U, gq.t() @ ref, gu.t() @ X, gu.t() @ U]
+            else:
+                cots = [gP, gA, gq[:, :, None] * X[:, None, :], gq * U[:, None], gq[:, :, None] * ref[:, None, :],
+                        gu[:, :, None] * X[:, None, :], gu * U[:, None]]
+            cots = [c.contiguous() for c in cots]
+            grads = [torch.empty_like(t) for t in plant]
+            condense_vjp_device(kp, nx, n, s_rows, [t.data_ptr() for t in plant], [c.data_ptr() for c in cots],
+                                [t.data_ptr() for t in grads], stream, solver.device)
+            grads = [t if need else None for t, need in zip(grads, ctx.needs_input_grad[3:10])]
+        dX = dU = dref = None
+        if ctx.ops is not None:
+            ops = ctx.ops
+            p = "k" if kp == 1 else "b"
+            dX = torch.einsum(f"{p}ij,bi->bj", ops["Fx"], gq) + torch.einsum(f"{p}ij,bi->bj", ops["Sbar"], gu)
+            dU = (ops["Fu"] * gq).sum(dim=1) + (ops["Ku"] * gu).sum(dim=1)
+            dref = torch.einsum(f"{p}it,bi->bt", ops["Fr"], gq)
+        return (None, None, None, *grads, dX, dU, dref)
+
+
+def mpc_plant_solution(solver, Ad, Bd, Cd, K, Q, R, RD, X, U, ref, s_rows=10, setup=True):
+    """One MPC step as a differentiable function of the plant model, the cost weights and the constraint row as
+    well as of the step's data: device fp64 tensors Ad (k, nx, nx), Bd, Cd, K (k, nx), Q, R, RD (k,) with
+    k = ``solver.n_plants`` (1: one plant shared by the batch, or batch: one per QP), X (batch, nx), U (batch),
+    ref (batch, n); ``solver.n`` is the horizon N and ``solver.m == 2 N``.  Returns ``(x, status)`` as
+    ``mpc_solution`` does; the caller's U is left alone.
+
+    Forward: ``solver.mpc_setup_plants_device`` on the tensors' own memory (condensing and setup on the device, no
+    host copy of the plant or the operators), then ``mpc_step_ref_device``.  With ``setup=False`` the caller
+    vouches that the solver already holds these plants (a second step on the same model) and only the step runs.
+    Backward: one ``sensitivity_data_device`` call (gq, gu, gP, gA), the operator cotangents gFx = gq X', gFu = gq U,
+    gFr = gq ref', gSbar = gu X', gKu = gu U in torch, and one ``condense_vjp_device`` call.  A
+    shared plant receives the sums over the batch.  A per-plant solver's backward pass materialises per-QP operator
+    cotangents, O(batch N^2) doubles (gP, gA, gFr and their kin).  The gradient is that of the QP's optimum at the
+    active set of the solve's final iterate: exact under strict complementarity, and zero for every QP that did not
+    end SOLVED.  Gradients with respect to X, U and ref are ``mpc_solution``'s chain rule; they need the condensed
+    operators, which are then fetched once per forward pass through the host (``solvempc_amd.condense``), only when
+    one of the three requires a gradient.  ``backward`` must run before the solver solves again."""
+    return _MpcPlantSolution.apply(solver, s_rows, setup, Ad, Bd, Cd, K, Q, R, RD, X, U, ref)
 
 
 def qp_solution(solver, P, A, q, l, u, setup=True):

@@ -80,6 +80,48 @@ def condense(plants: dict, N: int, s_rows: int = S_ROWS, device: int = 0) -> dic
     return out
 
 
+PLANT_KEYS = ("Ad", "Bd", "Cd", "K", "Q", "R", "RD")
+COTANGENT_KEYS = ("P", "A", "Fx", "Fu", "Fr", "Sbar", "Ku")  # (W0 is constant: no cotangent)
+
+
+def condense_vjp(plants: dict, cotangents: dict, N: int, s_rows: int = S_ROWS, device: int = 0) -> dict:
+    """The reverse of ``condense`` on the device (mpcq_condense_vjp): ``cotangents`` holds dL/d
+    operator for any of P, A, Fx, Fu, Fr, Sbar, Ku (leading plant axis, the shapes ``condense`` returns; a missing
+    key or None counts as zero); returns dL/d plant datum for Ad (k,nx,nx), Bd, Cd, K (k,nx) and Q, R, RD (k,).
+    gP is the cotangent of the full symmetric P."""
+    Ad = np.ascontiguousarray(plants["Ad"], dtype=np.float64)
+    k, nx = Ad.shape[0], Ad.shape[1]
+    ins = [Ad] + [np.ascontiguousarray(plants[key], dtype=np.float64).reshape(k, -1) for key in ("Bd", "Cd", "K")]
+    ins += [np.ascontiguousarray(plants[key], dtype=np.float64).reshape(k) for key in ("Q", "R", "RD")]
+    shapes = {"P": (k, N, N), "A": (k, 2 * N, N), "Fx": (k, N, nx), "Fu": (k, N), "Fr": (k, N, N),
+              "Sbar": (k, 2 * N, nx), "Ku": (k, 2 * N)}
+    unknown = set(cotangents) - set(shapes)
+    if unknown:
+        raise ValueError(f"condense_vjp: no cotangent for {sorted(unknown)} (one of {COTANGENT_KEYS})")
+    cots = [None if cotangents.get(key) is None else
+            np.ascontiguousarray(cotangents[key], dtype=np.float64).reshape(shapes[key]) for key in COTANGENT_KEYS]
+    out = {"Ad": np.zeros((k, nx, nx)), "Bd": np.zeros((k, nx)), "Cd": np.zeros((k, nx)), "K": np.zeros((k, nx)),
+           "Q": np.zeros(k), "R": np.zeros(k), "RD": np.zeros(k)}
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+    rc = _capi.lib().mpcq_condense_vjp(device, k, nx, N, s_rows, *[dp(a) for a in ins], *[dp(a) for a in cots],
+                                       *[dp(out[key]) for key in PLANT_KEYS])
+    _capi.check(rc, "mpcq_condense_vjp")
+    return out
+
+
+def condense_vjp_device(n_plants: int, nx: int, N: int, s_rows: int, plant_ptrs, cotangent_ptrs, out_ptrs,
+                        stream: int | None = None, device: int = 0) -> None:
+    """Same on device-resident fp64 buffers (mpcq_condense_vjp_device): three sequences of seven integer
+    pointers in the order Ad, Bd, Cd, K, Q, R, RD / gP, gA, gFx, gFu, gFr, gSbar, gKu / gAd, gBd, gCd, gK, gQ, gR,
+    gRD; a cotangent or an output may be 0 (not all of either).  Asynchronous on ``stream``; stateless."""
+    ptrs = [C.c_void_p(p or 0) for seq in (plant_ptrs, cotangent_ptrs, out_ptrs) for p in seq]
+    if len(ptrs) != 21:
+        raise ValueError("condense_vjp_device: seven plant, seven cotangent and seven output pointers")
+    rc = _capi.lib().mpcq_condense_vjp_device(int(device), int(n_plants), int(nx), int(N), int(s_rows), *ptrs,
+                                              C.c_void_p(stream or 0))
+    _capi.check(rc, "mpcq_condense_vjp_device")
+
+
 class ModelPredictiveControlAPI:
     """ModelPredictiveControlAPI(verbose) of the reference, batched over ``batch`` plant states."""
 
