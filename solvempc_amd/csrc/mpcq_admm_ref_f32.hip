@@ -3,9 +3,7 @@
 #define MPCQ_LANE_REF 1
 #include "mpcq_admm.h"
 
-extern "C" int mpcq_internal_admm_ref_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const mpcq::RefArgs *ref,
-                                                 hipStream_t s)
+template <> int mpcq::lane_unit<mpcq::Variant::Ref, float>(const AdmmArgs<float> &a, int nc, int mc, const RefArgs *ref, hipStream_t s)
 {
-    if (!ref || !ref->p) return -1;
-    return mpcq::launch_any<float>(*a, nc, mc, s, ref);
+    return launch_any<float>(a, nc, mc, s, ref);
 }

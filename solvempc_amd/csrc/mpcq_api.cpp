@@ -94,12 +94,29 @@ struct mpcq_ctx {
     bool all_ineq = true, mpc_ready = false, lower_free = false, fresh = false;
     double dinf_ks = 0.0, dinf_ku = 0.0;  // dual-infeasibility bounds (AdmmArgs::dinf_kappa), 0: none
     int cus = 256;                        // compute units of the device (phase lists)
-    // A tile-path controllerStep leaves q, u (the solver's data after updateGradient / updateUpperBound)
-    // as the step's saved X, U: d_q, d_u are filled from them by materialize_qu before anything reads
-    // them (a generic solve, the device view, an update, new operators).
+    // What the last solve left to be published on demand, and its order flag.
+    struct Lazy {
+        // a tile solve whose finalize stored only the warm state (x', z, y) and U: d_x, d_y are formed from it by
+        // materialize_xy before anything reads them (get_solution / get_dual, the device view, verbose, or a
+        // call that overwrites the warm state)
+        bool xy = false;
+        // the same solve's rho (fp64 contexts): its warm-state rho d_rhos is the reported one; d_rho is copied
+        // from it by materialize_rho before anything reads d_rho (get_info, the device view, verbose) or a
+        // reset overwrites d_rhos
+        bool rho = false;
+        // an ordered single-launch solve left status, iter in list-slot order: materialize_info permutes them
+        // into d_status, d_iter before anything reads those (get_info, the device view, verbose, the publish
+        // kernel of materialize_xy)
+        bool info = false;
+        // a tile-path controllerStep leaves q, u (the solver's data after updateGradient / updateUpperBound)
+        // as the step's saved X, U (d_Xs, d_Us) and its xref: d_q, d_u are filled from them by materialize_qu
+        // before anything reads them (a generic solve, the device view, an update, new operators)
+        bool qu = false;
+        double xref = 0.0;
+        bool ord = false;  // the last solve ran in the hardest-first order (mpcq_get_order)
+        void clear_results() { xy = rho = info = false; }  // a solve that writes every QP's x, y, rho, status, iter
+    } lazy;
     double *d_Xs = nullptr, *d_Us = nullptr;
-    bool qu_lazy = false;
-    double lazy_xref = 0.0;
     bool paired = false;  // shared plant of the condensed-MPC shape (tile kernel's paired loop)
     bool inv_ops = false; // per-plant operators in the direct-inverse reading (setup_inv_kernel): wave kernel only
     // tile (MFMA) path: shared plant with a compiled (KN, KM) shape
@@ -144,9 +161,9 @@ struct mpcq_ctx {
     size_t ref_cap = 0;
     double *d_ordG = nullptr;
     bool ordG_ok = false;
-    // what the captured step leaves lazy (x, y; rho; status, iter; q, u) and its order flag: every replay
-    // leaves the same, whatever a reader materialised in between
-    struct { bool xy, rho, info, qu, ord; double xref; } glazy{};
+    // what the captured step leaves lazy and its order flag: every replay leaves the same, whatever a reader
+    // materialised in between
+    Lazy glazy;
     // MIMO condensed MPC (mpcq_mimo.hip): per-plant operator block, dims
     double *d_mimo = nullptr;
     int mimo_N = 0, mimo_nx = 0, mimo_nu = 0, mimo_ny = 0, mimo_srows = 0, mimo_diag_k0 = 0;
@@ -173,20 +190,7 @@ struct mpcq_ctx {
     // plant, kept while the plant arrays are the same (pord_key); pord_ok when d_ordmap holds it
     bool pord_ok = false;
     struct { const double *Ad, *Bd, *Cd, *K, *Q, *R, *RD; int nx, s_rows; } pord_key{};
-    bool ord_last = false;  // the last solve ran in that order (mpcq_get_order)
-    bool ord_clean = false;  // its bin counters are zero (an ordered phase-0 launch clears them)
-    // a tile solve whose finalize stored only the warm state (x', z, y) and U: d_x, d_y are formed from it by
-    // materialize_xy before anything reads them (get_solution / get_dual, the device view, verbose, or a
-    // call that overwrites the warm state)
-    bool xy_lazy = false;
-    // the same solve's rho (fp64 contexts): its warm-state rho d_rhos is the reported one; d_rho is copied
-    // from it by materialize_rho before anything reads d_rho (get_info, the device view, verbose) or a
-    // reset overwrites d_rhos
-    bool rho_lazy = false;
-    // an ordered single-launch solve left status, iter in list-slot order: materialize_info permutes them
-    // into d_status, d_iter before anything reads those (get_info, the device view, verbose, the publish
-    // kernel of materialize_xy)
-    bool info_lazy = false;
+    bool ord_clean = false;  // the order's bin counters are zero (an ordered phase-0 launch clears them)
     // settings.polish (mpcq_polish.hip): status_polish and the reduced system's rows per QP, the returned
     // solution's (primal, dual) residual pairs; allocated only when polish is set.  pol_valid: the last solve
     // filled them (mpcq_get_polish_info reports "not performed" otherwise)
@@ -306,6 +310,22 @@ mpcq::AdmmArgs<T> make_args(mpcq_ctx *c)
         a.mix_r = *r ? std::max(1, std::atoi(r)) : MPCQ_MIX_R;
     }
     return a;
+}
+
+// The MPC front end's operators in the context (AdmmArgs reads them, CondenseArgs writes them).
+template <typename A>
+void set_front_end_ops(const mpcq_ctx *c, A &a)
+{
+    a.Fx = c->d_Fx; a.Fu = c->d_Fu; a.Fr = c->d_Fr; a.Sbar = c->d_Sbar; a.Ku = c->d_Ku; a.W0 = c->d_W0;
+}
+
+// An MPC step's front end (q = Fx X + Fu U + Fr ref, u = W0 + Sbar X + Ku U, then U += x(0)); where q, u or the
+// saved X, U go is the caller's choice.
+template <typename T>
+void set_mpc_front_end(const mpcq_ctx *c, mpcq::AdmmArgs<T> &a, const double *X, double *U, double xref)
+{
+    a.mpc = 1; a.mpc_u = 1; a.nx = c->nx; a.X = X; a.U = U; a.xref = xref;
+    set_front_end_ops(c, a);
 }
 
 int reset_state(mpcq_ctx *c, bool reset_rho)
@@ -605,7 +625,7 @@ static void dinf_bounds(mpcq_ctx *c, const double *blk, const mpcq::OpsLayout &L
 int setup_on_device(mpcq_ctx *c, hipStream_t s)
 {
     if (int rc = materialize_xy(c)) return rc;  // (with the images of the solve that left it)
-    c->qu_lazy = false;  // (q, u are re-broadcast from the setup data below)
+    c->lazy.qu = false;  // (q, u are re-broadcast from the setup data below)
     c->gen++;
     const size_t Pn = c->dims.n_plants, n = c->dims.n, m = c->dims.m, B = c->dims.batch;
     HIPCHK(hipMemsetAsync(c->d_ops, 0, 8 * Pn * c->ops_stride, s));
@@ -785,18 +805,13 @@ int mpcq_warm_start(mpcq_ctx *c, const double *x, const double *y)
     int rc = check_ctx(c, kGeneric);
     if (rc) return rc;
     if (!x || (c->dims.m && !y)) return fail(MPCQ_ERR_ARG, "null x/y");
-    c->xy_lazy = false;  // (x, y are staged in the output buffers below; a rejected call keeps a pending x, y)
+    c->lazy.xy = false;  // (x, y are staged in the output buffers below; a rejected call keeps a pending x, y)
     c->sens_ok = false;
     // stage in the output buffers (overwritten by the next solve)
     if ((rc = h2d(c->d_x, x, 8 * (size_t)c->dims.batch * c->dims.n, c->last))) return rc;
     if ((rc = h2d(c->d_y, y, 8 * (size_t)c->dims.batch * c->dims.m, c->last))) return rc;
-    if (c->dims.dtype == MPCQ_F32) {
-        auto a = make_args<float>(c);
-        rc = mpcq_internal_warm_f32(&a, c->nc, c->mc, c->d_x, c->d_y, c->last);
-    } else {
-        auto a = make_args<double>(c);
-        rc = mpcq_internal_warm_f64(&a, c->nc, c->mc, c->d_x, c->d_y, c->last);
-    }
+    rc = c->dims.dtype == MPCQ_F32 ? mpcq::launch_warm_start(make_args<float>(c), c->nc, c->mc, c->d_x, c->d_y, c->last)
+                                   : mpcq::launch_warm_start(make_args<double>(c), c->nc, c->mc, c->d_x, c->d_y, c->last);
     if (rc) return fail(MPCQ_ERR_HIP, "warm start kernel failed");
     HIPCHK(hipStreamSynchronize(c->last));
     return MPCQ_OK;
@@ -875,16 +890,28 @@ static int phase_stops(const mpcq_settings &st, int batch, int cus, int *stops, 
 
 static const char *env_kernel() { return test_hook("MPCQ_KERNEL"); }
 
+// The debug dump $MPCQ_TILE_STAMPS in the tools/stamps.py format: the header {phases, waves}, then the 8 stamps
+// of every wave, phase by phase.  Synchronises s.
+static int dump_tile_stamps(const char *path, const long long *d_stamps, size_t phases, size_t waves, hipStream_t s)
+{
+    std::vector<long long> h(8 * waves * phases);
+    if (hipMemcpyAsync(h.data(), d_stamps, 8 * h.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return -2;
+    if (FILE *f = std::fopen(path, "wb")) {
+        const long long hdr[2] = {(long long)phases, (long long)waves};
+        std::fwrite(hdr, 8, 2, f);
+        std::fwrite(h.data(), 8, h.size(), f);
+        std::fclose(f);
+    }
+    return 0;
+}
+
 template <typename T>
 static int wave_launch(mpcq_ctx *c, const mpcq::AdmmArgs<T> &a, int grid, hipStream_t s)
 {
-    if (c->cur_ref.p && a.mpc)  // an MPC front end with per-QP references: the REF variant
-        return std::is_same<T, float>::value
-                   ? mpcq_internal_wave_ref_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, grid, &c->cur_ref, s)
-                   : mpcq_internal_wave_ref_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, grid, &c->cur_ref, s);
-    return std::is_same<T, float>::value
-               ? mpcq_internal_wave_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, grid, s)
-               : mpcq_internal_wave_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, grid, s);
+    // (the reference: for an MPC front end with per-QP references, the REF variant)
+    return mpcq::launch_wave(a, c->nc, c->mc, grid, c->cur_ref.p && a.mpc ? &c->cur_ref : nullptr, s);
 }
 
 // The phase chain of a tile solve on stream s: phase p's QPs still running at its stop are appended to
@@ -901,7 +928,7 @@ static int launch_phases(mpcq_ctx *c, mpcq::AdmmArgs<T> &a, hipStream_t s, bool 
     const bool ordered = a.mpc && a.X && a.U && c->ord_ok && !wave_only && test_hook("MPCQ_ORDER")[0] != '0' &&
                          (!c->cur_ref.p || c->ordG_ok);
     const int np = phase_stops(c->set, B, c->cus, stops, &wave_tail, ordered);
-    c->ord_last = ordered;
+    c->lazy.ord = ordered;
     int *const ord_cnt = c->d_ord, *const ord_key = c->d_ord + mpcq::OrderBins::kBins, *const ord_list = ord_key + B;
     if (ordered) {
         // the counters are zero unless the last ordered sort's tile launch did not run (it clears them)
@@ -986,34 +1013,17 @@ static int launch_phases(mpcq_ctx *c, mpcq::AdmmArgs<T> &a, hipStream_t s, bool 
             break;
         }
         // every phase launches the phase-0 grid: list segment s is served by the blocks b % kShards == s
-        if (c->cur_ref.p && a.X)  // per-QP references: the REF variants (every phase re-forms q from X, U and ref)
-            rc = std::is_same<T, float>::value
-                     ? mpcq_internal_tile_ref_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, &c->cur_ref, s)
-                     : mpcq_internal_tile_ref_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, &c->cur_ref, s);
-        else
-            rc = std::is_same<T, float>::value
-                     ? mpcq_internal_tile_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, s)
-                     : mpcq_internal_tile_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, s);
+        // (per-QP references: the REF variant, whose every phase re-forms q from X, U and ref)
+        rc = mpcq::launch_tile(a, c->KN, c->KM, c->cur_ref.p && a.X ? &c->cur_ref : nullptr, s);
         if (rc) return rc;
         c->count0_clean = a.zero_cnt0 != nullptr;
         if (a.ord_zero) c->ord_clean = true;
         np_run = p + 1;
     }
-    c->xy_lazy = lazy_xy;
-    c->rho_lazy = lazy_xy && std::is_same<T, double>::value;
-    c->info_lazy = lazy_info;
-    if (stp && *stp) {
-        std::vector<long long> h(8 * waves * kMaxPhases);
-        if (hipMemcpyAsync(h.data(), c->d_stamps, 8 * h.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return -2;
-        if (FILE *f = std::fopen(stp, "wb")) {
-            const long long hdr[2] = {(long long)np_run, (long long)waves};
-            std::fwrite(hdr, 8, 2, f);
-            std::fwrite(h.data(), 8, 8 * waves * np_run, f);
-            std::fclose(f);
-        }
-    }
+    c->lazy.xy = lazy_xy;
+    c->lazy.rho = lazy_xy && std::is_same<T, double>::value;
+    c->lazy.info = lazy_info;
+    if (stp && *stp) return dump_tile_stamps(stp, c->d_stamps, np_run, waves, s);
     return 0;
 }
 
@@ -1043,15 +1053,8 @@ static int launch_args(mpcq_ctx *c, mpcq::AdmmArgs<T> &a, hipStream_t s)
 {
     const PathChoice p = choose_path(c);
     a.paired = p.paired;
-    if (p.kind == MPCQ_PATH_LANE) {
-        if (c->cur_ref.p && a.mpc)  // an MPC front end with per-QP references: the REF variant
-            return std::is_same<T, float>::value
-                       ? mpcq_internal_admm_ref_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, &c->cur_ref, s)
-                       : mpcq_internal_admm_ref_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, &c->cur_ref, s);
-        return std::is_same<T, float>::value
-                   ? mpcq_internal_admm_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, s)
-                   : mpcq_internal_admm_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, s);
-    }
+    if (p.kind == MPCQ_PATH_LANE)  // (the reference: for an MPC front end with per-QP references, the REF variant)
+        return mpcq::launch_lane(a, c->nc, c->mc, c->cur_ref.p && a.mpc ? &c->cur_ref : nullptr, s);
     if (!c->tile) {  // per-plant batches: one QP per wave (operators in VGPRs)
         a.stop_iter = c->set.max_iter;
         return wave_launch<T>(c, a, c->dims.batch, s);
@@ -1064,9 +1067,8 @@ static int launch_typed(mpcq_ctx *c, hipStream_t s, bool mpc, const double *X, d
 {
     auto a = make_args<T>(c);
     if (mpc) {
-        a.mpc = 1; a.mpc_u = 1; a.nx = c->nx; a.X = X; a.U = U; a.xref = xref;
+        set_mpc_front_end(c, a, X, U, xref);
         if (c->set.polish) a.mpc_u = 0;  // (the applied move is the polished one: polish_kernel's U += x[0])
-        a.Fx = c->d_Fx; a.Fu = c->d_Fu; a.Fr = c->d_Fr; a.Sbar = c->d_Sbar; a.Ku = c->d_Ku; a.W0 = c->d_W0;
         // (a step with per-QP references writes q, u eagerly on every path: q must outlive the caller's
         // reference buffer, and a saved window would need its own copy, buffer and front-end variant)
         const bool lazy = c->tile && choose_path(c).kind == MPCQ_PATH_TILE && c->d_Xs && c->d_Us && !c->cur_ref.p;
@@ -1075,8 +1077,8 @@ static int launch_typed(mpcq_ctx *c, hipStream_t s, bool mpc, const double *X, d
         } else {
             a.q_out = c->d_q; a.u_out = c->d_u;
         }
-        c->qu_lazy = lazy;
-        c->lazy_xref = xref;
+        c->lazy.qu = lazy;
+        c->lazy.xref = xref;
     }
     return launch_args<T>(c, a, s);
 }
@@ -1257,10 +1259,9 @@ extern "C" {
 static int launch_solve(mpcq_ctx *c, hipStream_t s, bool mpc, const double *X, double *U, double xref)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    c->ord_last = false;  // (launch_phases sets it for a hardest-first tile solve)
-    c->xy_lazy = false;   // (and this, for a chain that publishes x, y lazily)
-    c->rho_lazy = false;  // (the solve below writes d_rho, or leaves it lazy again)
-    c->info_lazy = false;  // (and d_status, d_iter: every solve writes every QP's)
+    c->lazy.ord = false;  // (launch_phases sets it for a hardest-first tile solve)
+    // (the solve below writes x, y, rho, status and iter of every QP, or launch_phases leaves them lazy again)
+    c->lazy.clear_results();
     const int rc = c->dims.dtype == MPCQ_F32 ? launch_typed<float>(c, s, mpc, X, U, xref)
                                              : launch_typed<double>(c, s, mpc, X, U, xref);
     if (rc) return fail(MPCQ_ERR_HIP, std::string("ADMM kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
@@ -1385,10 +1386,10 @@ int mpcq_get_stream_path(mpcq_ctx *c, int *kind)
 int mpcq_get_order(mpcq_ctx *c, int *ordered, int *order)
 {
     if (!c || !ordered) return fail(MPCQ_ERR_ARG, "null argument");
-    *ordered = c->ord_last ? 1 : 0;
+    *ordered = c->lazy.ord ? 1 : 0;
     if (order) {
         const size_t B = c->dims.batch;
-        if (!c->ord_last) {
+        if (!c->lazy.ord) {
             for (size_t i = 0; i < B; i++) order[i] = (int)i;
         } else {
             HIPCHK(hipMemcpyAsync(order, c->d_ord + mpcq::OrderBins::kBins + B, 4 * B, hipMemcpyDeviceToHost, c->last));
@@ -1446,10 +1447,10 @@ bool alloc_mpc_ops(mpcq_ctx *c, int nx)
 // d_q, d_u from the last tile-path controllerStep's saved X, U (mpcq_internal_front_end), once.
 static int materialize_qu(mpcq_ctx *c)
 {
-    if (!c->qu_lazy) return MPCQ_OK;
-    c->qu_lazy = false;
+    if (!c->lazy.qu) return MPCQ_OK;
+    c->lazy.qu = false;
     if (mpcq_internal_front_end((int)c->dims.batch, c->nx, (int)c->dims.n, (int)c->dims.m, c->d_Xs, c->d_Us,
-                                c->lazy_xref, c->d_Fx, c->d_Fu, c->d_Fr, c->d_Sbar, c->d_Ku, c->d_W0, c->d_q,
+                                c->lazy.xref, c->d_Fx, c->d_Fu, c->d_Fr, c->d_Sbar, c->d_Ku, c->d_W0, c->d_q,
                                 c->d_u, c->last) != 0)
         return fail(MPCQ_ERR_HIP, "front-end kernel launch failed");
     return MPCQ_OK;
@@ -1458,27 +1459,24 @@ static int materialize_qu(mpcq_ctx *c)
 // d_x, d_y of the last tile solve from its stored warm state (mpcq_tile.h tile_publish_kernel), once.
 static int materialize_xy(mpcq_ctx *c)
 {
-    if (!c->xy_lazy) return MPCQ_OK;
-    c->xy_lazy = false;
+    if (!c->lazy.xy) return MPCQ_OK;
+    c->lazy.xy = false;
     int rc = materialize_info(c);  // (the publish kernel reads each QP's status)
     if (rc) return rc;
-    if (c->dims.dtype == MPCQ_F32) {
-        auto a = make_args<float>(c);
-        a.img = (const float *)c->d_img;
-        rc = mpcq_internal_tile_publish_f32(&a, c->KN, c->KM, a.paired = c->paired && c->all_ineq && c->lower_free, c->last);
-    } else {
-        auto a = make_args<double>(c);
-        a.img = (const double *)c->d_img;
-        rc = mpcq_internal_tile_publish_f64(&a, c->KN, c->KM, a.paired = c->paired && c->all_ineq && c->lower_free, c->last);
-    }
+    auto publish = [c](auto a) {  // (a: the context's AdmmArgs<T>)
+        a.img = (decltype(a.img))c->d_img;
+        a.paired = c->paired && c->all_ineq && c->lower_free;
+        return mpcq::launch_tile_publish(a, c->KN, c->KM, a.paired != 0, c->last);
+    };
+    rc = c->dims.dtype == MPCQ_F32 ? publish(make_args<float>(c)) : publish(make_args<double>(c));
     return rc ? fail(MPCQ_ERR_HIP, "solution publish kernel failed") : MPCQ_OK;
 }
 
 // d_rho of the last tile solve from its warm-state rho (fp64: the same value), once.
 static int materialize_rho(mpcq_ctx *c)
 {
-    if (!c->rho_lazy) return MPCQ_OK;
-    c->rho_lazy = false;
+    if (!c->lazy.rho) return MPCQ_OK;
+    c->lazy.rho = false;
     HIPCHK(hipMemcpyAsync(c->d_rho, c->d_rhos, 8 * (size_t)c->dims.batch, hipMemcpyDeviceToDevice, c->last));
     return MPCQ_OK;
 }
@@ -1486,8 +1484,8 @@ static int materialize_rho(mpcq_ctx *c)
 // d_status, d_iter of the last ordered single-launch solve from its list-slot pairs, once.
 static int materialize_info(mpcq_ctx *c)
 {
-    if (!c->info_lazy) return MPCQ_OK;
-    c->info_lazy = false;
+    if (!c->lazy.info) return MPCQ_OK;
+    c->lazy.info = false;
     const int B = c->dims.batch;
     const int *list = c->d_ord + mpcq::OrderBins::kBins + B;
     if (mpcq_internal_order_info(B, list, list + B, c->d_status, c->d_iter, c->last) != 0)
@@ -2061,27 +2059,15 @@ template <typename T>
 static int launch_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, double xref, const mpcq::StreamArgs &sa,
                          const mpcq::LogArgs *lg)
 {
-    c->xy_lazy = false;  // (the stream writes every QP's x, y at its last step)
-    c->rho_lazy = false;  // (and rho)
-    c->info_lazy = false;  // (and status, iter)
+    c->lazy.clear_results();  // (the stream writes every QP's x, y, rho, status and iter at its last step)
     auto a = make_args<T>(c);
-    a.mpc = 1; a.mpc_u = 1; a.nx = c->nx; a.X = X; a.U = U; a.xref = xref;
-    a.Fx = c->d_Fx; a.Fu = c->d_Fu; a.Fr = c->d_Fr; a.Sbar = c->d_Sbar; a.Ku = c->d_Ku; a.W0 = c->d_W0;
+    set_mpc_front_end(c, a, X, U, xref);
     a.q_out = c->d_q; a.u_out = c->d_u;
     // (a reference schedule, c->cur_ref: the REF variant slides the window with the step)
     a.stop_iter = c->set.max_iter;
-    c->qu_lazy = false;
-    if (lg)  // a record is attached: the REF + LOG variant (a scalar run: the one-entry schedule [xref], mpc_run)
-        return std::is_same<T, float>::value
-                   ? mpcq_internal_stream_log_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, &sa, &c->cur_ref, lg, s)
-                   : mpcq_internal_stream_log_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, &sa, &c->cur_ref, lg, s);
-    if (c->cur_ref.p)
-        return std::is_same<T, float>::value
-                   ? mpcq_internal_stream_ref_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, &sa, &c->cur_ref, s)
-                   : mpcq_internal_stream_ref_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, &sa, &c->cur_ref, s);
-    return std::is_same<T, float>::value
-               ? mpcq_internal_stream_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->nc, c->mc, &sa, s)
-               : mpcq_internal_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->nc, c->mc, &sa, s);
+    c->lazy.qu = false;
+    // (a record is attached, lg: the REF + LOG variant; a scalar run: the one-entry schedule [xref], mpc_run)
+    return mpcq::launch_wave_stream(a, c->nc, c->mc, sa, c->cur_ref.p ? &c->cur_ref : nullptr, lg, s);
 }
 extern "C" {
 
@@ -2096,9 +2082,7 @@ template <typename T>
 static int launch_tile_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, double xref, mpcq::StreamArgs sa,
                               const mpcq::LogArgs *lg)
 {
-    c->xy_lazy = false;  // (the stream writes every QP's x, y at its last step)
-    c->rho_lazy = false;  // (and rho)
-    c->info_lazy = false;  // (and status, iter)
+    c->lazy.clear_results();  // (the stream writes every QP's x, y, rho, status and iter at its last step)
     const mpcq_settings &st = c->set;
     const int ct = st.check_termination;
     auto a = make_args<T>(c);
@@ -2115,8 +2099,7 @@ static int launch_tile_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, 
     // taken only when the waves fit one per SIMD
     const long waves = ((long)c->dims.batch + sa.cpw - 1) / sa.cpw;
     sa.occ = (waves <= simds && test_hook("MPCQ_STREAM_OCC")[0] == '1') ? 1 : 2;
-    a.mpc = 1; a.mpc_u = 1; a.nx = c->nx; a.X = X; a.U = U; a.xref = xref;
-    a.Fx = c->d_Fx; a.Fu = c->d_Fu; a.Fr = c->d_Fr; a.Sbar = c->d_Sbar; a.Ku = c->d_Ku; a.W0 = c->d_W0;
+    set_mpc_front_end(c, a, X, U, xref);
     a.X_save = c->d_Xs; a.U_save = c->d_Us;  // the last step's X, U: its q, u on demand (materialize_qu)
     if (c->cur_ref.p) {  // a reference schedule: the last step's q, u themselves (its window is not kept)
         a.X_save = a.U_save = nullptr;
@@ -2138,37 +2121,16 @@ static int launch_tile_stream(mpcq_ctx *c, hipStream_t s, double *X, double *U, 
             return -2;
         a.stamps = c->d_stamps;
     }
-    const int rc =
-        lg && c->cur_ref.p  // a record is attached: the REF kernel's LOG variant, or the scalar kernel's
-            ? (std::is_same<T, float>::value
-                   ? mpcq_internal_tile_reflog_stream_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, &c->cur_ref, lg, s)
-                   : mpcq_internal_tile_reflog_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, &c->cur_ref, lg, s))
-        : lg ? (std::is_same<T, float>::value
-                    ? mpcq_internal_tile_log_stream_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, lg, s)
-                    : mpcq_internal_tile_log_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, lg, s))
-        : c->cur_ref.p ? (std::is_same<T, float>::value
-                       ? mpcq_internal_tile_ref_stream_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, &c->cur_ref, s)
-                       : mpcq_internal_tile_ref_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, &c->cur_ref, s))
-                : (std::is_same<T, float>::value
-                       ? mpcq_internal_tile_stream_launch_f32((const mpcq::AdmmArgs<float> *)&a, c->KN, c->KM, s)
-                       : mpcq_internal_tile_stream_launch_f64((const mpcq::AdmmArgs<double> *)&a, c->KN, c->KM, s));
+    // (a reference schedule: the REF variant; a record is attached, lg: the scalar or the REF kernel's LOG variant)
+    const int rc = mpcq::launch_tile_stream(a, c->KN, c->KM, c->cur_ref.p ? &c->cur_ref : nullptr, lg, s);
     if (rc == 0 && stp && *stp) {
-        std::vector<long long> h(8 * swaves);
-        if (hipMemcpyAsync(h.data(), c->d_stamps, 8 * h.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return -2;
-        if (FILE *f = std::fopen(stp, "wb")) {
-            const long long hdr[2] = {1, (long long)swaves};
-            std::fwrite(hdr, 8, 2, f);
-            std::fwrite(h.data(), 8, h.size(), f);
-            std::fclose(f);
-        }
+        if (dump_tile_stamps(stp, c->d_stamps, 1, swaves, s)) return -2;
         (void)hipFree(c->d_stamps);
         c->d_stamps = nullptr;
     }
     if (rc == 0) {
-        c->qu_lazy = !c->cur_ref.p;
-        c->lazy_xref = xref;
+        c->lazy.qu = !c->cur_ref.p;
+        c->lazy.xref = xref;
     }
     return rc;
 }
@@ -2319,17 +2281,12 @@ static int mpc_run(mpcq_ctx *c, const char *fn, double *X, double *U, double xre
             return fail(MPCQ_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei));
         }
         c->gkey = {X, U, xref, noise_std, seed, first_qp, s, c->gen, sched, sched_len, sched_stride};
-        c->glazy = {c->xy_lazy, c->rho_lazy, c->info_lazy, c->qu_lazy, c->ord_last, c->lazy_xref};
+        c->glazy = c->lazy;
     }
     for (int k = done; k < steps; k++) {
         const auto t0 = std::chrono::steady_clock::now();
         HIPCHK(hipGraphLaunch(c->gexec, s));
-        c->xy_lazy = c->glazy.xy;
-        c->rho_lazy = c->glazy.rho;
-        c->info_lazy = c->glazy.info;
-        c->qu_lazy = c->glazy.qu;
-        c->ord_last = c->glazy.ord;
-        c->lazy_xref = c->glazy.xref;
+        c->lazy = c->glazy;
         if (sync_each && (rc = stage(("graph replay " + std::to_string(k)).c_str()))) return rc;
         if (c->set.verbose) {  // (the captured solve printed nothing: launch_solve)
             HIPCHK(hipStreamSynchronize(s));
@@ -2566,7 +2523,7 @@ int mpcq_mpc_setup_plants_device(mpcq_ctx *c, int nx, int s_rows, const double *
     a.s_rows = s_rows;
     a.Ad = Ad; a.Bd = Bd; a.Cd = Cd; a.K = K; a.Q = Q; a.R = R; a.RD = RD;
     a.P = c->d_P; a.A = c->d_A;
-    a.Fx = c->d_Fx; a.Fu = c->d_Fu; a.Fr = c->d_Fr; a.Sbar = c->d_Sbar; a.Ku = c->d_Ku; a.W0 = c->d_W0;
+    set_front_end_ops(c, a);
     a.q0 = c->d_q0; a.l0 = c->d_l0; a.u0 = c->d_u0;
     double *scr = nullptr;
     if (n > 32 && hipMalloc((void **)&scr, 8 * Pn * mpcq_internal_condense_scratch(nx, (int)n)) != hipSuccess)
@@ -2644,7 +2601,7 @@ int mpcq_mpc_plants_step_device(mpcq_ctx *c, int nx, int s_rows, const double *A
     hipStream_t s = (hipStream_t)stream;
     // the kernel below rewrites x, y, rho, status and iter of every QP on `s`: a pending lazy publication of an
     // earlier solve is dropped, not formed (it would be wasted work, and on another stream unordered with s)
-    c->xy_lazy = c->rho_lazy = c->info_lazy = false;
+    c->lazy.clear_results();
     if (c->last && c->last != s) {  // (the earlier solve's work on its stream before this one's writes)
         hipEvent_t ev;
         HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -2709,7 +2666,7 @@ int mpcq_mpc_plants_step_device(mpcq_ctx *c, int nx, int s_rows, const double *A
         }
     }
     if (ordered) c->ord_clean = true;
-    c->ord_last = ordered;
+    c->lazy.ord = ordered;
     c->mode = mpcq_ctx::Mode::OneShot;  // results only: no operator blocks were written
     c->sens_ok = false;
     c->mpc_ready = false;

@@ -510,7 +510,138 @@ struct SensChainArgs {
 };
 }  // namespace mpcq
 
-// Launchers (extern "C" so the host library links them without templates).
+// ---- Launchers of the ADMM kernel families, typed on T.
+// Every family's kernels are compiled once per variant and dtype, each pair in a translation unit of its own
+// (mpcq_<family>[_ref|_log|_reflog]_f32.hip / _f64.hip; mpcq_tile.h MPCQ_TILE_KERNEL says why the split is per
+// unit).  A unit defines its pair's piece of the family: an explicit specialisation of the family's *_unit
+// template on (Variant, T).  The launch_* dispatchers pick the piece from the pointers they are handed, so which
+// variant a call needs is decided here and nowhere else:
+//     a reference with data (ref && ref->p): Ref;  a record (lg): Log;  both: RefLog;  neither: Scalar
+// (a null or empty reference never reaches a REF unit).  The callers pass the reference only where the kernel's
+// front end reads it (mpcq_api.cpp).  Return codes: 0 launched, -1 the variant or the shape (capacity, (KN, KM),
+// the tile stream's paired condensed-MPC shape) is not compiled, -2 HIP error.
+namespace mpcq {
+enum class Variant { Scalar, Ref, Log, RefLog };
+inline Variant variant_of(const RefArgs *ref, const LogArgs *lg = nullptr)
+{
+    const bool r = ref && ref->p;
+    return lg ? (r ? Variant::RefLog : Variant::Log) : (r ? Variant::Ref : Variant::Scalar);
+}
+
+// One QP per lane (mpcq_admm.h): capacity (nc, mc) of MPCQ_CAPS.
+template <Variant V, typename T>
+int lane_unit(const AdmmArgs<T> &a, int nc, int mc, const RefArgs *ref, hipStream_t s);
+// One QP per wave (mpcq_wave.h): grid blocks of 64 threads stride over the (listed) QPs; n <= 32, m <= 64.
+template <Variant V, typename T>
+int wave_unit(const AdmmArgs<T> &a, int nc, int mc, int grid, const RefArgs *ref, hipStream_t s);
+// The receding-horizon stream in one launch (mpcq_wave.h stream_wave_kernel): every wave owns one QP for all
+// sa.steps control steps (solve, U += x0, plant update).
+template <Variant V, typename T>
+int wave_stream_unit(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa, const RefArgs *ref, const LogArgs *lg,
+                     hipStream_t s);
+// Tile (MFMA) path for a shared plant (mpcq_tile.h), shape (KN, KM) of MPCQ_TILE_SHAPES: one phase launch, and
+// the receding-horizon stream in one launch (AdmmArgs::sim; every column one plant through all its control steps).
+template <Variant V, typename T>
+int tile_unit(const AdmmArgs<T> &a, int KN, int KM, const RefArgs *ref, hipStream_t s);
+template <Variant V, typename T>
+int tile_stream_unit(const AdmmArgs<T> &a, int KN, int KM, const RefArgs *ref, const LogArgs *lg, hipStream_t s);
+// osqp_warm_start from the unscaled x, y (mpcq_admm_f32.hip / _f64.hip), and the lazily published x, y of the last
+// tile solve from its stored warm state (tile_publish_kernel, mpcq_tile_f32.hip / _f64.hip): no variants.
+template <typename T>
+int launch_warm_start(const AdmmArgs<T> &a, int nc, int mc, const double *x, const double *y, hipStream_t s);
+template <typename T>
+int launch_tile_publish(const AdmmArgs<T> &a, int KN, int KM, bool paired, hipStream_t s);
+
+// The compiled pieces (one line per translation unit and family).
+#define MPCQ_DECLARE_UNITS(T)                                                                                           \
+    template <> int lane_unit<Variant::Scalar, T>(const AdmmArgs<T> &, int, int, const RefArgs *, hipStream_t);         \
+    template <> int lane_unit<Variant::Ref, T>(const AdmmArgs<T> &, int, int, const RefArgs *, hipStream_t);            \
+    template <> int wave_unit<Variant::Scalar, T>(const AdmmArgs<T> &, int, int, int, const RefArgs *, hipStream_t);    \
+    template <> int wave_unit<Variant::Ref, T>(const AdmmArgs<T> &, int, int, int, const RefArgs *, hipStream_t);       \
+    template <> int wave_stream_unit<Variant::Scalar, T>(const AdmmArgs<T> &, int, int, const StreamArgs &,             \
+                                                         const RefArgs *, const LogArgs *, hipStream_t);                \
+    template <> int wave_stream_unit<Variant::Ref, T>(const AdmmArgs<T> &, int, int, const StreamArgs &,                \
+                                                      const RefArgs *, const LogArgs *, hipStream_t);                   \
+    template <> int wave_stream_unit<Variant::RefLog, T>(const AdmmArgs<T> &, int, int, const StreamArgs &,             \
+                                                         const RefArgs *, const LogArgs *, hipStream_t);                \
+    template <> int tile_unit<Variant::Scalar, T>(const AdmmArgs<T> &, int, int, const RefArgs *, hipStream_t);         \
+    template <> int tile_unit<Variant::Ref, T>(const AdmmArgs<T> &, int, int, const RefArgs *, hipStream_t);            \
+    template <> int tile_stream_unit<Variant::Scalar, T>(const AdmmArgs<T> &, int, int, const RefArgs *,                \
+                                                         const LogArgs *, hipStream_t);                                 \
+    template <> int tile_stream_unit<Variant::Ref, T>(const AdmmArgs<T> &, int, int, const RefArgs *, const LogArgs *,  \
+                                                      hipStream_t);                                                     \
+    template <> int tile_stream_unit<Variant::Log, T>(const AdmmArgs<T> &, int, int, const RefArgs *, const LogArgs *,  \
+                                                      hipStream_t);                                                     \
+    template <> int tile_stream_unit<Variant::RefLog, T>(const AdmmArgs<T> &, int, int, const RefArgs *,                \
+                                                         const LogArgs *, hipStream_t);                                 \
+    template <> int launch_warm_start<T>(const AdmmArgs<T> &, int, int, const double *, const double *, hipStream_t);   \
+    template <> int launch_tile_publish<T>(const AdmmArgs<T> &, int, int, bool, hipStream_t);
+MPCQ_DECLARE_UNITS(float)
+MPCQ_DECLARE_UNITS(double)
+#undef MPCQ_DECLARE_UNITS
+
+// (the lane, wave and tile phase kernels have no LOG variants: the record is the streams')
+template <typename T>
+inline int launch_lane(const AdmmArgs<T> &a, int nc, int mc, const RefArgs *ref, hipStream_t s)
+{
+    return variant_of(ref) == Variant::Ref ? lane_unit<Variant::Ref, T>(a, nc, mc, ref, s)
+                                           : lane_unit<Variant::Scalar, T>(a, nc, mc, ref, s);
+}
+template <typename T>
+inline int launch_wave(const AdmmArgs<T> &a, int nc, int mc, int grid, const RefArgs *ref, hipStream_t s)
+{
+    return variant_of(ref) == Variant::Ref ? wave_unit<Variant::Ref, T>(a, nc, mc, grid, ref, s)
+                                           : wave_unit<Variant::Scalar, T>(a, nc, mc, grid, ref, s);
+}
+template <typename T>
+inline int launch_tile(const AdmmArgs<T> &a, int KN, int KM, const RefArgs *ref, hipStream_t s)
+{
+    return variant_of(ref) == Variant::Ref ? tile_unit<Variant::Ref, T>(a, KN, KM, ref, s)
+                                           : tile_unit<Variant::Scalar, T>(a, KN, KM, ref, s);
+}
+template <typename T>
+inline int launch_wave_stream(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa, const RefArgs *ref,
+                              const LogArgs *lg, hipStream_t s)
+{
+    switch (variant_of(ref, lg)) {
+    case Variant::Scalar: return wave_stream_unit<Variant::Scalar, T>(a, nc, mc, sa, ref, lg, s);
+    case Variant::Ref: return wave_stream_unit<Variant::Ref, T>(a, nc, mc, sa, ref, lg, s);
+    case Variant::RefLog: return wave_stream_unit<Variant::RefLog, T>(a, nc, mc, sa, ref, lg, s);
+    case Variant::Log: break;  // not compiled: a logged scalar run hands the one-entry schedule [xref] (mpc_run)
+    }
+    return -1;
+}
+template <typename T>
+inline int launch_tile_stream(const AdmmArgs<T> &a, int KN, int KM, const RefArgs *ref, const LogArgs *lg, hipStream_t s)
+{
+    switch (variant_of(ref, lg)) {
+    case Variant::Scalar: return tile_stream_unit<Variant::Scalar, T>(a, KN, KM, ref, lg, s);
+    case Variant::Ref: return tile_stream_unit<Variant::Ref, T>(a, KN, KM, ref, lg, s);
+    case Variant::Log: return tile_stream_unit<Variant::Log, T>(a, KN, KM, ref, lg, s);
+    case Variant::RefLog: return tile_stream_unit<Variant::RefLog, T>(a, KN, KM, ref, lg, s);
+    }
+    return -1;
+}
+
+// The smallest of a list of compiled capacities (by NC (NC + MC)) that holds an n x m QP: false when none does
+// (*nc, *mc untouched).
+struct Cap { int nc, mc; };
+#define MPCQ_CAP_ITEM(NC_, MC_) {NC_, MC_},
+template <int K>
+inline bool smallest_cap(const Cap (&caps)[K], int n, int m, int *nc, int *mc)
+{
+    int best = -1;
+    for (const Cap &c : caps)
+        if (n <= c.nc && m <= c.mc && (best < 0 || c.nc * (c.nc + c.mc) < best)) {
+            best = c.nc * (c.nc + c.mc);
+            *nc = c.nc;
+            *mc = c.mc;
+        }
+    return best >= 0;
+}
+}  // namespace mpcq
+
+// Launchers that are not typed on T (extern "C" so the host library links them without templates).
 extern "C" {
 // OSQP polish of every SOLVED QP (mpcq_polish.hip; n <= 32, m <= 64): 0 launched, -1 unsupported shape,
 // -2 HIP error (*err).  cus: compute units of the device (grid size).
@@ -534,74 +665,8 @@ int mpcq_internal_condense_launch(const mpcq::CondenseArgs *a, hipStream_t s);
 size_t mpcq_internal_condense_scratch(int nx, int N);
 // 0 launched, -1 a shape the kernel does not serve (N > 32, nx > 8), -2 the launch failed.
 int mpcq_internal_condense_vjp_launch(const mpcq::CondenseVjpArgs *a, hipStream_t s);
-int mpcq_internal_admm_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, hipStream_t s);
-int mpcq_internal_admm_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, hipStream_t s);
-// The REF variants of the launchers (mpcq_*_ref_*.hip: the same kernels compiled with a per-QP horizon
-// reference, RefArgs, as a trailing kernel argument; the lane kernel here, the wave, stream and tile kernels
-// below).  Same return codes; -1 also for a null reference.
-int mpcq_internal_admm_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const mpcq::RefArgs *ref,
-                                      hipStream_t s);
-int mpcq_internal_admm_ref_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const mpcq::RefArgs *ref,
-                                      hipStream_t s);
-int mpcq_internal_warm_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const double *x, const double *y,
-                           hipStream_t s);
-int mpcq_internal_warm_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const double *x, const double *y,
-                           hipStream_t s);
-// Tile (MFMA) path for a shared plant: 0 = launched, -1 = (KN, KM) not compiled, -2 = HIP error.
+// Tile (MFMA) path for a shared plant: 1 when (KN, KM) is compiled.
 int mpcq_internal_tile_supported(int KN, int KM);
-int mpcq_internal_tile_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, hipStream_t s);
-int mpcq_internal_tile_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, hipStream_t s);
-// The lazily published x, y of the last tile solve from its stored warm state (mpcq_tile.h tile_publish_kernel).
-int mpcq_internal_tile_publish_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, int paired, hipStream_t s);
-int mpcq_internal_tile_publish_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, int paired, hipStream_t s);
-// The receding-horizon stream in one tile launch (AdmmArgs::sim; every column one plant through all its
-// control steps).  0 launched, -1 not the paired condensed-MPC shape.
-int mpcq_internal_tile_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, hipStream_t s);
-int mpcq_internal_tile_stream_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, hipStream_t s);
-// The same launches with a per-QP horizon reference (the tile kernel's REF variants, mpcq_tile_ref_f64.hip /
-// mpcq_tile_ref_f32.hip); same return codes.
-int mpcq_internal_tile_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, const mpcq::RefArgs *ref,
-                                      hipStream_t s);
-int mpcq_internal_tile_ref_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, const mpcq::RefArgs *ref,
-                                      hipStream_t s);
-int mpcq_internal_tile_ref_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, const mpcq::RefArgs *ref,
-                                             hipStream_t s);
-int mpcq_internal_tile_ref_stream_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, const mpcq::RefArgs *ref,
-                                             hipStream_t s);
-// One-QP-per-wave path (mpcq_wave.h): grid blocks of 64 threads stride over the (listed) QPs;
-// -1 = n > 32 or m > 64 (not compiled).
-int mpcq_internal_wave_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, int grid, hipStream_t s);
-int mpcq_internal_wave_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, int grid, hipStream_t s);
-int mpcq_internal_wave_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, int grid, const mpcq::RefArgs *ref,
-                                      hipStream_t s);
-int mpcq_internal_wave_ref_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, int grid, const mpcq::RefArgs *ref,
-                                      hipStream_t s);
-// The receding-horizon stream in one launch (mpcq_wave.h stream_wave_kernel): every wave owns one QP
-// for all `steps` control steps (solve, U += x0, plant update).  0 launched, -1 no compiled capacity.
-int mpcq_internal_stream_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const mpcq::StreamArgs *sa,
-                                    hipStream_t s);
-int mpcq_internal_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const mpcq::StreamArgs *sa,
-                                    hipStream_t s);
-int mpcq_internal_stream_ref_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const mpcq::StreamArgs *sa,
-                                        const mpcq::RefArgs *ref, hipStream_t s);
-int mpcq_internal_stream_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const mpcq::StreamArgs *sa,
-                                        const mpcq::RefArgs *ref, hipStream_t s);
-// The one-launch streams with a per-step record: the stream kernels compiled once more with LogArgs as a further
-// trailing kernel argument.  Tile: the scalar kernel's LOG variant (mpcq_tile_log_*.hip) and the REF kernel's
-// (mpcq_tile_reflog_*.hip).  One QP per wave: the REF kernel's only (mpcq_wave_log_*.hip), which a scalar-xref run
-// hands the one-entry schedule [xref].  Same return codes; -1 also for a null reference or record.
-int mpcq_internal_tile_log_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, const mpcq::LogArgs *lg,
-                                             hipStream_t s);
-int mpcq_internal_tile_log_stream_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, const mpcq::LogArgs *lg,
-                                             hipStream_t s);
-int mpcq_internal_tile_reflog_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, const mpcq::RefArgs *ref,
-                                                const mpcq::LogArgs *lg, hipStream_t s);
-int mpcq_internal_tile_reflog_stream_launch_f32(const mpcq::AdmmArgs<float> *a, int KN, int KM, const mpcq::RefArgs *ref,
-                                                const mpcq::LogArgs *lg, hipStream_t s);
-int mpcq_internal_stream_log_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const mpcq::StreamArgs *sa,
-                                        const mpcq::RefArgs *ref, const mpcq::LogArgs *lg, hipStream_t s);
-int mpcq_internal_stream_log_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const mpcq::StreamArgs *sa,
-                                        const mpcq::RefArgs *ref, const mpcq::LogArgs *lg, hipStream_t s);
 // One row of the record from the context's buffers (mpcq_log.hip; the per-step graph, after the step's plant
 // update): U, X as they stand, status and iter of the step's solve.
 int mpcq_internal_log_row(int nx, const double *X, const double *U, const int *status, const int *iter,

@@ -483,7 +483,8 @@ __device__ __forceinline__ void reg_mv(const T (&m1)[kRegMvTiles<T, REM, NTO>][K
 // admm_tile_reflog_kernel, whose stream mode writes the per-step record (LogArgs, the last kernel argument) from
 // its once-per-control-step code: U, status and iter of a column's finished step at its finalize (lane group 0),
 // the plant's new X in stream_next (lane group g: components g, g + 4).  Those units instantiate the stream
-// launchers only.
+// launchers only.  Each unit defines its (variant, dtype) piece of mpcq_internal.h's tile_unit / tile_stream_unit;
+// launch_tile / launch_tile_stream there pick the piece from a call's reference and record pointers.
 #if defined(MPCQ_TILE_LOG) && defined(MPCQ_TILE_REF)
 #define MPCQ_TILE_KERNEL admm_tile_reflog_kernel
 #define MPCQ_TILE_REF_PARAM , RefArgs ref, LogArgs lg

@@ -1,17 +1,18 @@
 // solvempc_amd/csrc/mpcq_tile_f64.hip — fp64 instantiations of the tile (MFMA) ADMM kernel.
 #include "mpcq_tile.h"
 
-extern "C" int mpcq_internal_tile_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, hipStream_t s)
+template <> int mpcq::tile_unit<mpcq::Variant::Scalar, double>(const AdmmArgs<double> &a, int KN, int KM, const RefArgs *, hipStream_t s)
 {
-    return mpcq::tile_launch_any<double>(*a, KN, KM, s);
+    return tile_launch_any<double>(a, KN, KM, s);
 }
 
-extern "C" int mpcq_internal_tile_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, hipStream_t s)
+template <> int mpcq::tile_stream_unit<mpcq::Variant::Scalar, double>(const AdmmArgs<double> &a, int KN, int KM, const RefArgs *,
+                                                                       const LogArgs *, hipStream_t s)
 {
-    return mpcq::tile_stream_launch_any<double>(*a, KN, KM, s);
+    return tile_stream_launch_any<double>(a, KN, KM, s);
 }
 
-extern "C" int mpcq_internal_tile_publish_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, int paired, hipStream_t s)
+template <> int mpcq::launch_tile_publish<double>(const AdmmArgs<double> &a, int KN, int KM, bool paired, hipStream_t s)
 {
-    return mpcq::tile_publish_any<double>(*a, KN, KM, paired != 0, s);
+    return tile_publish_any<double>(a, KN, KM, paired, s);
 }

@@ -3,9 +3,8 @@
 #define MPCQ_TILE_LOG 1
 #include "mpcq_tile.h"
 
-extern "C" int mpcq_internal_tile_log_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, const mpcq::LogArgs *lg,
-                                                        hipStream_t s)
+template <> int mpcq::tile_stream_unit<mpcq::Variant::Log, double>(const AdmmArgs<double> &a, int KN, int KM, const RefArgs *,
+                                                                    const LogArgs *lg, hipStream_t s)
 {
-    if (!lg) return -1;
-    return mpcq::tile_stream_launch_any<double>(*a, KN, KM, s, nullptr, lg);
+    return tile_stream_launch_any<double>(a, KN, KM, s, nullptr, lg);
 }

@@ -3,16 +3,13 @@
 #define MPCQ_TILE_REF 1
 #include "mpcq_tile.h"
 
-extern "C" int mpcq_internal_tile_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM, const mpcq::RefArgs *ref,
-                                                 hipStream_t s)
+template <> int mpcq::tile_unit<mpcq::Variant::Ref, double>(const AdmmArgs<double> &a, int KN, int KM, const RefArgs *ref, hipStream_t s)
 {
-    if (!ref || !ref->p) return -1;
-    return mpcq::tile_launch_any<double>(*a, KN, KM, s, ref);
+    return tile_launch_any<double>(a, KN, KM, s, ref);
 }
 
-extern "C" int mpcq_internal_tile_ref_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM,
-                                                        const mpcq::RefArgs *ref, hipStream_t s)
+template <> int mpcq::tile_stream_unit<mpcq::Variant::Ref, double>(const AdmmArgs<double> &a, int KN, int KM, const RefArgs *ref,
+                                                                    const LogArgs *, hipStream_t s)
 {
-    if (!ref || !ref->p) return -1;
-    return mpcq::tile_stream_launch_any<double>(*a, KN, KM, s, ref);
+    return tile_stream_launch_any<double>(a, KN, KM, s, ref);
 }

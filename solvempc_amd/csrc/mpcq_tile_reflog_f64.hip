@@ -4,9 +4,8 @@
 #define MPCQ_TILE_LOG 1
 #include "mpcq_tile.h"
 
-extern "C" int mpcq_internal_tile_reflog_stream_launch_f64(const mpcq::AdmmArgs<double> *a, int KN, int KM,
-                                                           const mpcq::RefArgs *ref, const mpcq::LogArgs *lg, hipStream_t s)
+template <> int mpcq::tile_stream_unit<mpcq::Variant::RefLog, double>(const AdmmArgs<double> &a, int KN, int KM, const RefArgs *ref,
+                                                                       const LogArgs *lg, hipStream_t s)
 {
-    if (!ref || !ref->p || !lg) return -1;
-    return mpcq::tile_stream_launch_any<double>(*a, KN, KM, s, ref, lg);
+    return tile_stream_launch_any<double>(a, KN, KM, s, ref, lg);
 }

@@ -148,7 +148,9 @@ __device__ __noinline__ void build_minv(const T *ops, const int *ctype, const Op
 // (as in mpcq_tile.h: a split per unit, not a shared body behind a wrapper).
 // MPCQ_WAVE_LOG on top of MPCQ_WAVE_REF (mpcq_wave_log_*.hip; mpcq_mpc_set_stream_log): the REF stream kernel's text
 // once more as stream_wave_reflog_kernel, which writes the per-step record (LogArgs, a further trailing argument)
-// after each control step's fences.  Those units instantiate the stream launcher only.
+// after each control step's fences.  Those units instantiate the stream launcher only.  Each unit defines its
+// (variant, dtype) piece of mpcq_internal.h's wave_unit / wave_stream_unit; launch_wave / launch_wave_stream there
+// pick the piece from a call's reference and record pointers (no LOG-only piece: -1).
 #if defined(MPCQ_WAVE_LOG) && !defined(MPCQ_WAVE_REF)
 #error "MPCQ_WAVE_LOG builds on MPCQ_WAVE_REF"
 #endif
@@ -705,13 +707,9 @@ static int wave_launch(const AdmmArgs<T> &a, int nc, int mc, int grid, hipStream
 template <typename T>
 static int wave_launch_any(const AdmmArgs<T> &a, int nc, int mc, int grid, hipStream_t s, const RefArgs *ref = nullptr)
 {
-    int best = -1, bn = 0, bm = 0;
-#define MPCQ_PICK(NC_, MC_)                                                  \
-    if (a.n <= NC_ && a.m <= MC_ && (best < 0 || NC_ * (NC_ + MC_) < best)) { \
-        best = NC_ * (NC_ + MC_); bn = NC_; bm = MC_;                         \
-    }
-    MPCQ_WAVE_CAPS(MPCQ_PICK)
-#undef MPCQ_PICK
+    static constexpr Cap caps[] = {MPCQ_WAVE_CAPS(MPCQ_CAP_ITEM)};
+    int bn = 0, bm = 0;
+    if (!smallest_cap(caps, a.n, a.m, &bn, &bm)) return -1;
 #define MPCQ_TRY(NC_, MC_) if (bn == NC_ && bm == MC_) return wave_launch<T, NC_, MC_>(a, nc, mc, grid, s, ref);
     MPCQ_WAVE_CAPS(MPCQ_TRY)
 #undef MPCQ_TRY
@@ -722,13 +720,9 @@ template <typename T>
 static int stream_launch_any(const AdmmArgs<T> &a, int nc, int mc, const StreamArgs &sa, hipStream_t s, const RefArgs *ref = nullptr,
                              const LogArgs *lg = nullptr)
 {
-    int best = -1, bn = 0, bm = 0;
-#define MPCQ_PICK(NC_, MC_)                                                  \
-    if (a.n <= NC_ && a.m <= MC_ && (best < 0 || NC_ * (NC_ + MC_) < best)) { \
-        best = NC_ * (NC_ + MC_); bn = NC_; bm = MC_;                         \
-    }
-    MPCQ_WAVE_CAPS(MPCQ_PICK)
-#undef MPCQ_PICK
+    static constexpr Cap caps[] = {MPCQ_WAVE_CAPS(MPCQ_CAP_ITEM)};
+    int bn = 0, bm = 0;
+    if (!smallest_cap(caps, a.n, a.m, &bn, &bm)) return -1;
 #define MPCQ_TRY(NC_, MC_) if (bn == NC_ && bm == MC_) return stream_launch<T, NC_, MC_>(a, nc, mc, sa, s, ref, lg);
     MPCQ_WAVE_CAPS(MPCQ_TRY)
 #undef MPCQ_TRY

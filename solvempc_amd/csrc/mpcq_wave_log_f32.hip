@@ -4,9 +4,8 @@
 #define MPCQ_WAVE_LOG 1
 #include "mpcq_wave.h"
 
-extern "C" int mpcq_internal_stream_log_launch_f32(const mpcq::AdmmArgs<float> *a, int nc, int mc, const mpcq::StreamArgs *sa,
-                                                   const mpcq::RefArgs *ref, const mpcq::LogArgs *lg, hipStream_t s)
+template <> int mpcq::wave_stream_unit<mpcq::Variant::RefLog, float>(const AdmmArgs<float> &a, int nc, int mc, const StreamArgs &sa,
+                                                                      const RefArgs *ref, const LogArgs *lg, hipStream_t s)
 {
-    if (!ref || !ref->p || !lg) return -1;
-    return mpcq::stream_launch_any<float>(*a, nc, mc, *sa, s, ref, lg);
+    return stream_launch_any<float>(a, nc, mc, sa, s, ref, lg);
 }

@@ -3,16 +3,13 @@
 #define MPCQ_WAVE_REF 1
 #include "mpcq_wave.h"
 
-extern "C" int mpcq_internal_wave_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, int grid,
-                                                 const mpcq::RefArgs *ref, hipStream_t s)
+template <> int mpcq::wave_unit<mpcq::Variant::Ref, double>(const AdmmArgs<double> &a, int nc, int mc, int grid, const RefArgs *ref, hipStream_t s)
 {
-    if (!ref || !ref->p) return -1;
-    return mpcq::wave_launch_any<double>(*a, nc, mc, grid, s, ref);
+    return wave_launch_any<double>(a, nc, mc, grid, s, ref);
 }
 
-extern "C" int mpcq_internal_stream_ref_launch_f64(const mpcq::AdmmArgs<double> *a, int nc, int mc, const mpcq::StreamArgs *sa,
-                                                   const mpcq::RefArgs *ref, hipStream_t s)
+template <> int mpcq::wave_stream_unit<mpcq::Variant::Ref, double>(const AdmmArgs<double> &a, int nc, int mc, const StreamArgs &sa,
+                                                                    const RefArgs *ref, const LogArgs *, hipStream_t s)
 {
-    if (!ref || !ref->p) return -1;
-    return mpcq::stream_launch_any<double>(*a, nc, mc, *sa, s, ref);
+    return stream_launch_any<double>(a, nc, mc, sa, s, ref);
 }
