@@ -211,6 +211,28 @@ public:
         u_ = uv;
         return true;
     }
+    /* osqp_update_P / osqp_update_A on the device (mpcq_update_P_A, rescale = 1: equilibrated again, as OSQP
+     * does): the QP keeps its gradient and bounds and the next solve is warm-started from the last solution.  A
+     * new sparsity pattern is simply a new dense matrix.  The Data object keeps the new matrix, as osqp-eigen's,
+     * also when the update fails: after a false return for a matrix the device rejected (not positive definite,
+     * MPCQ_ERR_SETUP) Data holds that matrix and the solver is unusable until clearSolver() + initSolver(), which
+     * then set up on it -- hand Data a valid matrix first. */
+    template <typename Derived>
+    bool updateHessianMatrix(const Eigen::SparseCompressedBase<Derived> &H)
+    {
+        if (!ctx_) return fail("updateHessianMatrix: the solver is not initialised");
+        if (!data_->setHessianMatrix(H)) return fail("updateHessianMatrix: wrong size");
+        const RowMajor P = data_->P_;
+        return mpcq_update_P_A(ctx_, P.data(), nullptr, 1) == MPCQ_OK || fail("updateHessianMatrix");
+    }
+    template <typename Derived>
+    bool updateLinearConstraintsMatrix(const Eigen::SparseCompressedBase<Derived> &A)
+    {
+        if (!ctx_) return fail("updateLinearConstraintsMatrix: the solver is not initialised");
+        if (!data_->m_ || !data_->setLinearConstraintsMatrix(A)) return fail("updateLinearConstraintsMatrix: wrong size");
+        const RowMajor Ar = data_->A_;
+        return mpcq_update_P_A(ctx_, nullptr, Ar.data(), 1) == MPCQ_OK || fail("updateLinearConstraintsMatrix");
+    }
     /* osqp_warm_start(x, y) */
     bool setWarmStart(const Eigen::Ref<const Eigen::VectorXd> &x, const Eigen::Ref<const Eigen::VectorXd> &y)
     {

@@ -144,6 +144,48 @@ int mpcq_update_bounds(mpcq_ctx *ctx, const double *l, const double *u);
 int mpcq_warm_start(mpcq_ctx *ctx, const double *x, const double *y);
 int mpcq_cold_start(mpcq_ctx *ctx);
 
+/* New matrices for a context that is set up: osqp_update_P / osqp_update_A / osqp_update_P_A (osqp-eigen's
+ * updateHessianMatrix / updateLinearConstraintsMatrix), from device memory, with a warm start.
+ * P_dev: n_plants*n*n (upper triangle read, as mpcq_setup), A_dev: n_plants*m*n, fp64 device pointers; either may
+ * be NULL, which keeps the context's current matrix.  Serves a context set up by mpcq_setup or
+ * mpcq_mpc_setup_plants_device: shared-plant and per-plant, every dtype and solve path.  Runs on `stream`, ordered
+ * after the context's last stream (an event), and becomes the context's last stream: the next solve is ordered
+ * after it.  The only host transfer is the setup's flag word with plant 0's operator block, as in
+ * mpcq_mpc_setup_plants_device.
+ * Afterwards, for both values of `rescale`:
+ *   - every QP keeps its current q, l, u (a tile-path step's lazy q, u are formed first); nothing is re-broadcast
+ *     from the setup's q0, l0, u0, which still give the constraint types and the q0 the cost scaling sees;
+ *   - the next solve starts from the previous unscaled (x, y) exactly as mpcq_warm_start(x_prev, y_prev) would
+ *     install them under the new matrices and scaling (x^ = D^-1 x, y^ = c E^-1 y, z^ = A^ x^); a QP whose previous
+ *     x or y holds a non-finite entry (infeasible, non-convex) starts cold (x = z = y = 0).  The previous (x, y)
+ *     are those of the context's last solve, a stream run (mpcq_mpc_run*_device: its last control step) included,
+ *     or the arguments of a later mpcq_warm_start.  A context that has not solved or been warm-started since its
+ *     setup, or since its last mpcq_cold_start, starts cold as a whole: a cold start asked for before the update
+ *     stands.  A pending mpcq_reset still applies to the next solve;
+ *   - every QP's rho is settings.rho again.  A stated deviation: OSQP keeps rho_vec and leaves its iterates in the
+ *     old scaled coordinates, neither of which means anything across a new scaling;
+ *   - the outputs (x, y, status, iter, rho) keep the last solve's values until the next solve;
+ *     mpcq_get_polish_info reports "not performed", mpcq_sensitivity* return MPCQ_ERR_ORDER until then;
+ *   - the MPC operators (Fx .. W0) and the stream plant are kept: a caller whose plant changed calls
+ *     mpcq_mpc_set_operators as before.  The hardest-first order map follows the new matrices.
+ * rescale = 1 (OSQP's behaviour): scale_data and the KKT basis run again on the new matrices with the setup's q0:
+ *   the setup kernels of mpcq_setup on the new data; every generic shape.
+ * rescale = 0 (the fast path): D, E, c, the rows' rho scales and constraint types stay bit for bit what the
+ *   last setup left (mpcq_get_scaling returns the same bits); only the factor stage is rebuilt (Cholesky, Jacobi
+ *   eigen-basis and operator products of a shared plant; M(rho) and its inverse per plant), one wavefront per
+ *   plant.  The new matrices are scaled once, each product rounded left to right in fp64:
+ *     P^_ij = (D_i * (c * P_ij)) * D_j      (P symmetrised from its upper triangle first)
+ *     A^_ij = (E_i * A_ij) * D_j
+ *   Needs n <= 32 and m <= 64.
+ * MPCQ_ERR_ORDER: no setup yet, or after mpcq_mpc_plants_step_device.  MPCQ_ERR_ARG: both matrices NULL (on a
+ * context with m == 0, which has no A: P NULL); a MIMO
+ * context; rescale not 0 or 1; rescale = 0 with n > 32 or m > 64; `stream` under graph capture.  A refused call
+ * writes nothing.  MPCQ_ERR_SETUP: the new P^ + sigma I (+ rho A^'A^) is not positive definite; the context then
+ * needs mpcq_setup (solves return MPCQ_ERR_ORDER), as OSQP's workspace is unusable after a failed update. */
+int mpcq_update_P_A_device(mpcq_ctx *ctx, const double *P_dev, const double *A_dev, int rescale, void *stream);
+/* Host-memory form (copies in on the context's last stream, synchronises). */
+int mpcq_update_P_A(mpcq_ctx *ctx, const double *P, const double *A, int rescale);
+
 /* Return every QP to the state right after setup (x = z = y = 0, rho = settings.rho), as
  * re-running initSolver (:64) would; applied by the next solve at no cost. */
 int mpcq_reset(mpcq_ctx *ctx);

@@ -122,6 +122,28 @@ class BatchSolver:
     def cold_start(self) -> None:
         _capi.check(lib().mpcq_cold_start(self._ctx), "mpcq_cold_start")
 
+    # -- new matrices with a warm start (osqp_update_P_A; updateHessianMatrix / updateLinearConstraintsMatrix)
+    def update_P_A(self, P=None, A=None, rescale: bool = True) -> None:
+        """New P (n_plants, n, n; upper triangle read) and / or A (n_plants, m, n) for a solver that is set up;
+        None keeps the current matrix.  Every QP keeps its q, l, u and the next solve is warm-started from the
+        previous (x, y); rho returns to settings.rho.  ``rescale=True`` equilibrates again (OSQP's behaviour),
+        ``rescale=False`` keeps the scaling of the last setup and rebuilds the factors alone (n <= 32, m <= 64)."""
+        k = self.n_plants
+        Pp = Ap = None
+        if P is not None:
+            P = _c64(P).reshape(k, self.n, self.n)
+            Pp = _dp(P)
+        if A is not None:
+            A = _c64(A).reshape(k, self.m, self.n)
+            Ap = _dp(A)
+        _capi.check(lib().mpcq_update_P_A(self._ctx, Pp, Ap, int(bool(rescale))), "mpcq_update_P_A")
+
+    def update_P_A_device(self, P_ptr: int = 0, A_ptr: int = 0, rescale: int = 1, stream: int | None = None) -> None:
+        """Same from device-resident fp64 buffers (0 keeps the current matrix); asynchronous on ``stream``, ordered
+        after the solver's last stream, and the next solve is ordered after it."""
+        _capi.check(lib().mpcq_update_P_A_device(self._ctx, C.c_void_p(P_ptr or 0), C.c_void_p(A_ptr or 0), int(rescale),
+                                                 C.c_void_p(stream or 0)), "mpcq_update_P_A_device")
+
     def reset_state(self) -> None:
         """Back to the post-setup state (x = z = y = 0, rho = settings.rho) for the next solve."""
         _capi.check(lib().mpcq_reset(self._ctx), "mpcq_reset")

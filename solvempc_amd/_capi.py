@@ -26,6 +26,10 @@ EXPORTS = (
     "mpcq_sensitivity_device", "mpcq_sensitivity", "mpcq_mpc_step_gains_device", "mpcq_mpc_step_gains",
     "mpcq_sensitivity_data_device", "mpcq_sensitivity_data", "mpcq_condense_vjp_device", "mpcq_condense_vjp",
 )
+# The symbols whose names follow OSQP's capitals (osqp_update_P_A).  They are kept apart from EXPORTS because the
+# header scan of tests/test_abi.py, which EXPORTS must equal, reads lower-case names only; lib() binds them with
+# the rest and so fails loudly on a library that lacks them (tests/test_update_P_A_ref.py checks header and mirror).
+EXPORTS_OSQP_CASE = ("mpcq_update_P_A_device", "mpcq_update_P_A")
 
 
 class MpcqError(RuntimeError):
@@ -91,6 +95,8 @@ def lib() -> C.CDLL:
         "mpcq_update_bounds": (C.c_int, [vp, dp, dp]),
         "mpcq_warm_start": (C.c_int, [vp, dp, dp]),
         "mpcq_cold_start": (C.c_int, [vp]),
+        "mpcq_update_P_A_device": (C.c_int, [vp, vp, vp, C.c_int, vp]),
+        "mpcq_update_P_A": (C.c_int, [vp, dp, dp, C.c_int]),
         "mpcq_reset": (C.c_int, [vp]),
         "mpcq_solve": (C.c_int, [vp, vp]),
         "mpcq_get_solution": (C.c_int, [vp, dp]),

@@ -203,6 +203,10 @@ struct mpcq_ctx {
     // allocated on first use (g, gq: batch*n; gl, gu: batch*m; dX: batch*8; dU: batch; dref: batch*n; then
     // batch ints).  sens_ev orders a caller's stream after the context's last stream and back.
     bool sens_ok = false;
+    // d_x, d_y hold (or a pending publish will give) the (x, y) that mpcq_update_P_A_device warm-starts from: set by
+    // every solve (launch_solve, the one-launch stream runs, whose last step writes them) and by mpcq_warm_start,
+    // which stages its arguments there; cleared by every setup and by mpcq_cold_start (the update then starts cold)
+    bool have_xy = false;
     double *d_sens = nullptr;
     hipEvent_t sens_ev = nullptr;
     // mpcq_sensitivity_data*: the shared plant's partial sums, then the host form's gP, gA (grown on demand)
@@ -619,16 +623,39 @@ static void dinf_bounds(mpcq_ctx *c, const double *blk, const mpcq::OpsLayout &L
     c->dinf_ku = dinv_min * mu / (std::sqrt((double)n) * dmax);
 }
 
-// Setup kernels on the device-resident setup data (d_P, d_q0, d_A, d_l0, d_u0), operator
-// conversion / tile images, per-QP broadcast of q0/u0/l0, state reset and the plant-0 scaling
-// readback.  One 4-byte flag word (non-convex plant, non-inequality row) comes back to the host.
+// setup_on_device: setup kernels on the device-resident setup data (d_P, d_q0, d_A, d_l0, d_u0), operator
+// conversion / tile images, the plant-0 scaling readback (run_setup), then the per-QP broadcast of q0/u0/l0 and
+// the state reset.  One 4-byte flag word (non-convex plant, non-inequality row) comes back to the host.
+// run_setup's options: keep_scaling: the keep-scaling kernels (mpcq_update_P_A_device,
+// rescale = 0), which rebuild the factor stage alone and leave D, E, c, the rho scales and the constraint types as
+// the operator blocks hold them.  check_lower / check_paired: the device-side checks of mpcq_update_P_A_device,
+// enqueued behind the setup kernel so that the one flag word carries their answers too (*flags_out).
+struct SetupRun {
+    bool keep_scaling = false, check_lower = false, check_paired = false;
+};
+
+int run_setup(mpcq_ctx *c, hipStream_t s, const SetupRun &run = SetupRun{}, int *flags_out = nullptr);
+
 int setup_on_device(mpcq_ctx *c, hipStream_t s)
 {
     if (int rc = materialize_xy(c)) return rc;  // (with the images of the solve that left it)
     c->lazy.qu = false;  // (q, u are re-broadcast from the setup data below)
-    c->gen++;
+    c->have_xy = false;
+    if (int rc = run_setup(c, s)) return rc;
     const size_t Pn = c->dims.n_plants, n = c->dims.n, m = c->dims.m, B = c->dims.batch;
-    HIPCHK(hipMemsetAsync(c->d_ops, 0, 8 * Pn * c->ops_stride, s));
+    const int per = Pn > 1;
+    if (mpcq_internal_broadcast(c->d_q0, c->d_q, (int)n, (int)B, per, s) ||
+        mpcq_internal_broadcast(c->d_u0, c->d_u, (int)m, (int)B, per, s) ||
+        mpcq_internal_broadcast(c->d_l0, c->d_l, (int)m, (int)B, per, s))
+        return fail(MPCQ_ERR_HIP, "broadcast failed");
+    return reset_state(c, true);
+}
+
+int run_setup(mpcq_ctx *c, hipStream_t s, const SetupRun &run, int *flags_out)
+{
+    c->gen++;
+    const size_t Pn = c->dims.n_plants, n = c->dims.n, m = c->dims.m;
+    if (!run.keep_scaling) HIPCHK(hipMemsetAsync(c->d_ops, 0, 8 * Pn * c->ops_stride, s));
     HIPCHK(hipMemsetAsync(c->d_flags, 0, 4, s));
     mpcq::SetupArgs a{};
     a.n = (int)n;
@@ -659,8 +686,9 @@ int setup_on_device(mpcq_ctx *c, hipStream_t s)
     const char *hook = test_hook("MPCQ_SETUP");
     const bool fits = mpcq_internal_setup_wave_lds((int)n, (int)m) != 0;
     const bool ref_setup = !std::strcmp(hook, "ref") || !fits;
-    c->inv_ops = !ref_setup && Pn > 1 && std::strcmp(hook, "eigen") != 0;
-    if (c->inv_ops) {
+    if (run.keep_scaling) {  // (in the reading the blocks were built in; the caller has checked that the plant fits)
+        if (mpcq_internal_setup_keep_launch(&a, c->inv_ops, s) != 0) return fail(MPCQ_ERR_HIP, "setup kernel launch failed");
+    } else if ((c->inv_ops = !ref_setup && Pn > 1 && std::strcmp(hook, "eigen") != 0)) {
         if (mpcq_internal_setup_inv_launch(&a, s) != 0) return fail(MPCQ_ERR_HIP, "setup kernel launch failed");
     } else if (ref_setup) {
         if (!c->d_scratch && hipMalloc((void **)&c->d_scratch, 8 * Pn * setup_scratch_len((int)n, (int)m)) != hipSuccess)
@@ -690,6 +718,11 @@ int setup_on_device(mpcq_ctx *c, hipStream_t s)
     }
     // plant-0 scaling (mpcq_get_scaling, host-side bound checks) and the flag word: one sync
     const mpcq::OpsLayout L = mpcq::OpsLayout::make(c->nc, c->mc);
+    if (run.check_lower &&
+        mpcq_internal_lower_free_check(c->d_l, c->d_ops + L.E, (int)m, (size_t)c->dims.batch * m, c->d_flags, s) != 0)
+        return fail(MPCQ_ERR_HIP, "lower-bound check kernel failed");
+    if (run.check_paired && mpcq_internal_paired_check(c->d_A, (int)(n * n), c->d_flags, s) != 0)
+        return fail(MPCQ_ERR_HIP, "paired-rows check kernel failed");
     std::vector<double> blk(c->ops_stride);
     int flags = 0;
     HIPCHK(hipMemcpyAsync(&flags, c->d_flags, 4, hipMemcpyDeviceToHost, s));
@@ -697,7 +730,8 @@ int setup_on_device(mpcq_ctx *c, hipStream_t s)
     HIPCHK(hipStreamSynchronize(s));
     if (flags & 1) return fail(MPCQ_ERR_SETUP, "setup: P + sigma I (+ rho A'A) not positive definite (non-convex QP)");
     if (flags & 4) return fail(MPCQ_ERR_SETUP, "setup: Jacobi eigen-solve of the KKT family did not converge in 60 sweeps");
-    c->all_ineq = !(flags & 2);
+    if (flags_out) *flags_out = flags;
+    if (!run.keep_scaling) c->all_ineq = !(flags & 2);  // (kept constraint types: the kept flag)
     for (size_t i = 0; i < n; i++) c->hD[i] = blk[L.D + i];
     for (size_t j = 0; j < m; j++) c->hE[j] = blk[L.E + j];
     c->hc = blk[L.cs];
@@ -708,12 +742,7 @@ int setup_on_device(mpcq_ctx *c, hipStream_t s)
     if (c->tile && mpcq_internal_tile_images(c->d_ops, c->nc, c->mc, c->KN, c->KM, c->dims.dtype == MPCQ_F32,
                                              c->d_img, s) != 0)
         return fail(MPCQ_ERR_HIP, "tile image kernel failed");
-    const int per = Pn > 1;
-    if (mpcq_internal_broadcast(c->d_q0, c->d_q, (int)n, (int)B, per, s) ||
-        mpcq_internal_broadcast(c->d_u0, c->d_u, (int)m, (int)B, per, s) ||
-        mpcq_internal_broadcast(c->d_l0, c->d_l, (int)m, (int)B, per, s))
-        return fail(MPCQ_ERR_HIP, "broadcast failed");
-    return reset_state(c, true);
+    return MPCQ_OK;
 }
 
 static int build_order_map(mpcq_ctx *c);  // (below: the hardest-first order of a tile-path MPC step)
@@ -795,6 +824,7 @@ int mpcq_cold_start(mpcq_ctx *c)
     int rc = check_ctx(c, kGeneric);
     if (rc) return rc;
     c->sens_ok = false;  // (the warm state is no longer the last solve's iterate)
+    c->have_xy = false;  // (a matrix update before the next solve keeps the cold start: mpcq_update_P_A_device)
     if ((rc = reset_state(c, false))) return rc;
     HIPCHK(hipStreamSynchronize(c->last));
     return MPCQ_OK;
@@ -813,6 +843,101 @@ int mpcq_warm_start(mpcq_ctx *c, const double *x, const double *y)
     rc = c->dims.dtype == MPCQ_F32 ? mpcq::launch_warm_start(make_args<float>(c), c->nc, c->mc, c->d_x, c->d_y, c->last)
                                    : mpcq::launch_warm_start(make_args<double>(c), c->nc, c->mc, c->d_x, c->d_y, c->last);
     if (rc) return fail(MPCQ_ERR_HIP, "warm start kernel failed");
+    HIPCHK(hipStreamSynchronize(c->last));
+    c->have_xy = true;
+    return MPCQ_OK;
+}
+
+// ---- osqp_update_P / osqp_update_A / osqp_update_P_A with a warm start (include/mpcq.h)
+namespace {
+
+// The refusals of include/mpcq.h, before anything is enqueued or written
+int update_check(mpcq_ctx *c, const char *fn, const void *P, const void *A, int rescale, hipStream_t s)
+{
+    if (!c) return fail(MPCQ_ERR_ARG, "null context");
+    if (c->mimo_only || c->mode == mpcq_ctx::Mode::Mimo)
+        return fail(MPCQ_ERR_ARG, std::string(fn) + ": MIMO contexts are not served");
+    int rc = check_ctx(c, kGeneric);
+    if (rc) return rc;
+    // (a context without constraints has no A: an A alone is then nothing to update)
+    if (!P && (!A || !c->dims.m)) return fail(MPCQ_ERR_ARG, std::string(fn) + ": P and A are both NULL");
+    if (rescale != 0 && rescale != 1) return fail(MPCQ_ERR_ARG, std::string(fn) + ": rescale must be 0 or 1");
+    if (rescale == 0 && !mpcq_internal_setup_wave_lds(c->dims.n, c->dims.m))
+        return fail(MPCQ_ERR_ARG, std::string(fn) + ": rescale = 0 serves n <= 32, m <= 64 (the keep-scaling kernels)");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return fail(MPCQ_ERR_ARG, std::string(fn) + ": the stream is under graph capture");
+    }
+    return MPCQ_OK;
+}
+
+// host: P, A are host arrays (copied before the call returns); otherwise device arrays read on s.
+int update_P_A(mpcq_ctx *c, const double *P, const double *A, bool host, int rescale, hipStream_t s)
+{
+    // what the last solve left lazy, published with the operators and images it ran on: q, u stay the QPs' own,
+    // x, y are the warm start, and rho, status, iter stay readable until the next solve
+    int rc = materialize_qu(c);
+    if (rc || (rc = materialize_xy(c)) || (rc = materialize_rho(c)) || (rc = materialize_info(c))) return rc;
+    if (s != c->last) {
+        if (!c->sens_ev) HIPCHK(hipEventCreateWithFlags(&c->sens_ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->sens_ev, c->last));
+        HIPCHK(hipStreamWaitEvent(s, c->sens_ev, 0));
+    }
+    c->last = s;
+    c->sens_ok = false;
+    c->pol_valid = false;
+    c->mode = mpcq_ctx::Mode::None;  // (until the new factors stand: a failed update needs mpcq_setup)
+    const size_t Pn = c->dims.n_plants, n = c->dims.n, m = c->dims.m, B = c->dims.batch;
+    if (!m) A = nullptr;
+    const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    if (P) HIPCHK(hipMemcpyAsync(c->d_P, P, 8 * Pn * n * n, kind, s));
+    if (A) HIPCHK(hipMemcpyAsync(c->d_A, A, 8 * Pn * m * n, kind, s));
+    if (host) HIPCHK(hipStreamSynchronize(s));
+    SetupRun run;
+    run.keep_scaling = rescale == 0;
+    // a shared plant's lower_free follows E (exact rule); a per-plant context's rule does not read the scaling
+    run.check_lower = Pn == 1 && m > 0;
+    run.check_paired = A && Pn == 1 && m == 2 * n && n % 4 == 0;
+    int flags = 0;
+    if ((rc = run_setup(c, s, run, &flags))) return rc;
+    if (A) c->paired = run.check_paired && !(flags & 16);
+    if (run.check_lower) c->lower_free = !(flags & 8);
+    // every QP's rho back to settings.rho; the warm state from the previous unscaled (x, y) under the new operators
+    const bool f32 = c->dims.dtype == MPCQ_F32;
+    const double r = std::min(std::max(c->set.rho, mpcq::kRhoMin), mpcq::kRhoMax);
+    if (mpcq_internal_fill(c->d_rhos, f32, r, B, s) != 0) return fail(MPCQ_ERR_HIP, "fill kernel failed");
+    if (c->have_xy) {
+        rc = f32 ? mpcq::launch_warm_start(make_args<float>(c), c->nc, c->mc, c->d_x, c->d_y, s)
+                 : mpcq::launch_warm_start(make_args<double>(c), c->nc, c->mc, c->d_x, c->d_y, s);
+        if (rc || mpcq_internal_cold_nonfinite(c->d_x, c->d_y, (int)n, (int)m, c->nc, c->mc, (int)B, f32, c->d_xs, c->d_zs,
+                                               c->d_ys, s) != 0)
+            return fail(MPCQ_ERR_HIP, "warm start kernel failed");
+    } else {
+        const size_t es = f32 ? 4 : 8;
+        HIPCHK(hipMemsetAsync(c->d_xs, 0, es * c->nc * B, s));
+        HIPCHK(hipMemsetAsync(c->d_zs, 0, es * c->mc * B, s));
+        HIPCHK(hipMemsetAsync(c->d_ys, 0, es * c->mc * B, s));
+    }
+    c->mode = mpcq_ctx::Mode::Generic;  // (gen: bumped once, by run_setup)
+    if ((rc = build_order_map(c))) return rc;  // (new P, A: the MPC step's order map, if operators are set)
+    verbose_header(c, rescale ? "mpcq_update_P_A (osqp_update_P_A: scaling, KKT basis, warm start)"
+                              : "mpcq_update_P_A (kept scaling: KKT basis, warm start)");
+    return MPCQ_OK;
+}
+
+}  // namespace
+
+int mpcq_update_P_A_device(mpcq_ctx *c, const double *P_dev, const double *A_dev, int rescale, void *stream)
+{
+    int rc = update_check(c, "mpcq_update_P_A_device", P_dev, A_dev, rescale, (hipStream_t)stream);
+    return rc ? rc : update_P_A(c, P_dev, A_dev, false, rescale, (hipStream_t)stream);
+}
+
+int mpcq_update_P_A(mpcq_ctx *c, const double *P, const double *A, int rescale)
+{
+    int rc = update_check(c, "mpcq_update_P_A", P, A, rescale, c ? c->last : nullptr);
+    if (rc || (rc = update_P_A(c, P, A, true, rescale, c->last))) return rc;
     HIPCHK(hipStreamSynchronize(c->last));
     return MPCQ_OK;
 }
@@ -1267,6 +1392,7 @@ static int launch_solve(mpcq_ctx *c, hipStream_t s, bool mpc, const double *X, d
     if (rc) return fail(MPCQ_ERR_HIP, std::string("ADMM kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
     c->last = s;
     c->fresh = false;
+    c->have_xy = true;
     c->pol_valid = false;
     c->sens_ok = !c->stream_acc;  // (a stream run's per-step solves are not served: mpcq_sensitivity_device)
     if (c->set.polish) {
@@ -2206,6 +2332,7 @@ static int mpc_run(mpcq_ctx *c, const char *fn, double *X, double *U, double xre
         if (lrc == 0) {
             if (mpcq_internal_set_step(c->d_step, first_step + steps, s)) return fail(MPCQ_ERR_HIP, "set_step launch failed");
             c->fresh = false;
+            c->have_xy = true;  // (the stream's last step wrote d_x, d_y)
             c->last = s;
             c->stream_path = MPCQ_STREAM_TILE;
             return stage("tile stream kernel");
@@ -2226,6 +2353,7 @@ static int mpc_run(mpcq_ctx *c, const char *fn, double *X, double *U, double xre
         if (lrc) return fail(MPCQ_ERR_HIP, std::string("stream kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
         if (mpcq_internal_set_step(c->d_step, first_step + steps, s)) return fail(MPCQ_ERR_HIP, "set_step launch failed");
         c->fresh = false;
+        c->have_xy = true;  // (the stream's last step wrote d_x, d_y)
         c->last = s;
         c->stream_path = MPCQ_STREAM_WAVE;
         return stage("stream kernel");

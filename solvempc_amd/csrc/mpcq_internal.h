@@ -117,7 +117,8 @@ struct SetupArgs {
     int *status;       // [plant] 0 ok, else error
     long long *prof;   // debug (MPCQ_SETUP_PROF): [plant][16] stage clock stamps, or null
     int *flags;        // OR over plants: 1 setup failed (non-convex), 2 a row is not an inequality,
-                       // 4 the Jacobi eigen-solve hit its sweep cap (inaccurate basis)
+                       // 4 the Jacobi eigen-solve hit its sweep cap (inaccurate basis); 8, 16: the checks of
+                       // mpcq_update_P_A_device (mpcq_internal_lower_free_check, mpcq_internal_paired_check)
 };
 
 // Phase lists of the tile path: the QPs a phase hands on are appended to one of kShards segments
@@ -657,6 +658,15 @@ int mpcq_internal_setup_wave_launch(const mpcq::SetupArgs *args, hipStream_t str
 // Per-plant setup with the direct inverse M(rho)^-1 (mpcq_setup_wave.hip; n <= 32, m <= 64).
 int mpcq_internal_setup_inv_launch(const mpcq::SetupArgs *args, hipStream_t stream);
 size_t mpcq_internal_setup_wave_lds(int n, int m);
+// mpcq_update_P_A_device (mpcq_setup_wave.hip).  The factor stage alone under the scaling the operator blocks hold
+// (inv: the direct-inverse reading); the device-side checks, which OR into the setup's flag word: 8 some QP's lower
+// bound is not free under the blocks' E, 16 A's lower half is not its negated upper half; and the cold start of
+// the QPs whose previous (x, y) is not finite.  0 launched, -1 unsupported shape, -2 HIP error.
+int mpcq_internal_setup_keep_launch(const mpcq::SetupArgs *args, int inv, hipStream_t stream);
+int mpcq_internal_lower_free_check(const double *l, const double *E, int m, size_t total, int *flags, hipStream_t stream);
+int mpcq_internal_paired_check(const double *A, int nn, int *flags, hipStream_t stream);
+int mpcq_internal_cold_nonfinite(const double *x, const double *y, int n, int m, int nc, int mc, int batch, int is_f32,
+                                 void *xs, void *zs, void *ys, hipStream_t stream);
 int mpcq_internal_f64_to_f32(const double *in, float *out, size_t count, hipStream_t s);
 int mpcq_internal_broadcast(const double *src, double *dst, int len, int batch, int per_qp_src, hipStream_t s);
 int mpcq_internal_fill(void *p, int is_f32, double v, size_t count, hipStream_t s);

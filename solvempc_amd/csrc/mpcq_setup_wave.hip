@@ -13,7 +13,11 @@
 //   * W = L^-T V, W^-1 = V' L', and the operator products element-parallel into the global block.
 // A single-wave workgroup makes every __syncthreads a wave-level ordering point (no s_barrier cost).
 // Shapes n <= 32, m <= 64 (the wave kernel's capacities); larger plants use setup_kernel.
+// setup_wave_keep_kernel / setup_inv_keep_kernel (mpcq_update_P_A_device, rescale = 0) are the same bodies with the
+// scaling read from the plant's operator block instead of recomputed: the factor stage alone on new matrices.
 #include "mpcq_internal.h"
+
+#include <algorithm>
 
 namespace mpcq {
 
@@ -172,7 +176,37 @@ __device__ double ruiz_and_types(const SetupArgs &a, int pl, int t, int n, int m
     return cost;
 }
 
-__global__ __launch_bounds__(64) void setup_wave_kernel(SetupArgs a)
+// The scaling stage of the keep-scaling kernels (mpcq_update_P_A_device, rescale = 0), in place of the data
+// load and ruiz_and_types: D, E, c and the rows' rho scales are those the plant's operator block holds (read,
+// never rewritten: they and ctype keep their bits), and the new matrices are scaled once,
+//   P^_ij = (D_i (c P_ij)) D_j,   A^_ij = (E_i A_ij) D_j     (left to right: three and two roundings),
+// P symmetrised from its upper triangle first.  On exit Ph, Ah, Dv, Ev and Et (rscale) are as ruiz_and_types
+// leaves them.
+__device__ inline void load_kept_scaling(const SetupArgs &a, int pl, int t, int n, int m, int ld, const double *blk,
+                                         const OpsLayout &Lo, double *Ph, double *Ah, double *Dv, double *Ev, double *Et)
+{
+    const double *P = a.P + (size_t)pl * n * n;
+    const double *A = a.A + (size_t)pl * m * n;
+    for (int j = t; j < n; j += 64) Dv[j] = blk[Lo.D + j];
+    for (int i = t; i < m; i += 64) { Ev[i] = blk[Lo.E + i]; Et[i] = blk[Lo.rscale + i]; }
+    const double c = blk[Lo.cs];
+    __syncthreads();
+    for (int e = t; e < n * n; e += 64) {
+        const int i = e / n, j = e % n;
+        const double p = (i <= j) ? P[i * n + j] : P[j * n + i];
+        Ph[i * ld + j] = (Dv[i] * (c * p)) * Dv[j];
+    }
+    for (int e = t; e < m * n; e += 64) {
+        const int i = e / n, j = e % n;
+        Ah[i * ld + j] = (Ev[i] * A[e]) * Dv[j];
+    }
+    __syncthreads();
+}
+
+// KEEP: the keep-scaling form (setup_wave_keep_kernel): load_kept_scaling for the stages up to ruiz_and_types,
+// the same factor stage, and nothing of the scaling written back.
+template <bool KEEP>
+__device__ __forceinline__ void setup_wave_body(const SetupArgs &a)
 {
     extern __shared__ double sm[];
     const int pl = blockIdx.x;
@@ -193,19 +227,24 @@ __global__ __launch_bounds__(64) void setup_wave_kernel(SetupArgs a)
     int *ctype = a.ctype + (size_t)pl * mc;
 
     MPCQ_STAMP(0);
-    // ---- data (osqp-eigen keeps the upper triangle of the Hessian)
-    for (int e = t; e < n * n; e += 64) {
-        const int i = e / n, j = e % n;
-        Ph[i * ld + j] = (i <= j) ? P[i * n + j] : P[j * n + i];
-    }
-    for (int e = t; e < m * n; e += 64) Ah[(e / n) * ld + e % n] = A[e];
-    for (int j = t; j < n; j += 64) { qh[j] = q0[j]; Dv[j] = 1.0; }
-    for (int i = t; i < m; i += 64) Ev[i] = 1.0;
-    if (t == 0) sh[0] = 1.0;
-    __syncthreads();
+    double cost = 1.0;
+    if constexpr (KEEP) {
+        load_kept_scaling(a, pl, t, n, m, ld, out, Lo, Ph, Ah, Dv, Ev, Et);
+    } else {
+        // ---- data (osqp-eigen keeps the upper triangle of the Hessian)
+        for (int e = t; e < n * n; e += 64) {
+            const int i = e / n, j = e % n;
+            Ph[i * ld + j] = (i <= j) ? P[i * n + j] : P[j * n + i];
+        }
+        for (int e = t; e < m * n; e += 64) Ah[(e / n) * ld + e % n] = A[e];
+        for (int j = t; j < n; j += 64) { qh[j] = q0[j]; Dv[j] = 1.0; }
+        for (int i = t; i < m; i += 64) Ev[i] = 1.0;
+        if (t == 0) sh[0] = 1.0;
+        __syncthreads();
 
-    MPCQ_STAMP(1);
-    const double cost = ruiz_and_types(a, pl, t, n, m, mc, ld, Ph, Ah, Dv, Ev, Dt, Et, qh, sh, ctype);
+        MPCQ_STAMP(1);
+        cost = ruiz_and_types(a, pl, t, n, m, mc, ld, Ph, Ah, Dv, Ev, Dt, Et, qh, sh, ctype);
+    }
     MPCQ_STAMP(3);
     // ---- P~ = P^ + sigma I + RHO_MIN sum_free a a' (into L), G = sum rscale a a' (into Tm)
     for (int e = t; e < n * n; e += 64) {
@@ -386,15 +425,19 @@ __global__ __launch_bounds__(64) void setup_wave_kernel(SetupArgs a)
     }
     for (int k = t; k < nc; k += 64) {
         o_lam[k] = k < n ? fmax(C[k * ld + k], 0.0) : 0.0;
-        o_D[k] = k < n ? Dv[k] : 1.0;
-        o_Dinv[k] = k < n ? 1.0 / Dv[k] : 1.0;
+        if constexpr (!KEEP) {
+            o_D[k] = k < n ? Dv[k] : 1.0;
+            o_Dinv[k] = k < n ? 1.0 / Dv[k] : 1.0;
+        }
     }
-    for (int i = t; i < mc; i += 64) {
-        o_E[i] = i < m ? Ev[i] : 1.0;
-        o_Einv[i] = i < m ? 1.0 / Ev[i] : 1.0;
-        o_rs[i] = i < m ? Et[i] : 1.0;
+    if constexpr (!KEEP) {
+        for (int i = t; i < mc; i += 64) {
+            o_E[i] = i < m ? Ev[i] : 1.0;
+            o_Einv[i] = i < m ? 1.0 / Ev[i] : 1.0;
+            o_rs[i] = i < m ? Et[i] : 1.0;
+        }
+        if (t == 0) { o_cs[0] = cost; o_cs[1] = 1.0 / cost; }
     }
-    if (t == 0) { o_cs[0] = cost; o_cs[1] = 1.0 / cost; }
     __syncthreads();
     for (int i = n - 1; i >= 0; i--) {  // (L')[r][i] = L[i][r]
         const double li = L[i * ld + i];
@@ -443,10 +486,15 @@ __global__ __launch_bounds__(64) void setup_wave_kernel(SetupArgs a)
     }
 }
 
+__global__ __launch_bounds__(64) void setup_wave_kernel(SetupArgs a) { setup_wave_body<false>(a); }
+// The factor stage alone on new matrices under the kept scaling (Cholesky, Jacobi eigen-basis, operator products).
+__global__ __launch_bounds__(64) void setup_wave_keep_kernel(SetupArgs a) { setup_wave_body<true>(a); }
+
 // In-place Gauss-Jordan inverse of an SPD matrix in LDS (n <= 32, row stride ld), 64 threads; no
 // pivoting (SPD: every pivot is positive).  Returns false when a pivot is not positive (P^ + sigma I
 // + rho A^'A^ not positive definite: OSQP's setup would fail to factor it).
-__device__ bool gj_invert_spd(double *M, int n, int ld, int t)
+// (forced inline: with two kernels calling it, a real call would cost each the worst-case register budget)
+__device__ __forceinline__ bool gj_invert_spd(double *M, int n, int ld, int t)
 {
     bool ok = true;
     for (int k = 0; k < n; k++) {
@@ -484,7 +532,8 @@ __device__ bool gj_invert_spd(double *M, int n, int ld, int t)
 // of the eigen-basis's Cholesky + Jacobi sweeps.  Writes the operator block in the direct-inverse
 // reading of OpsLayout (mpcq_internal.h): W = W^-1 = I, lambda = 0, sigma W'W = sigma M^-1,
 // G = M^-1, Bt = A^ M^-1, PW = P^, WtA = Ah = A^, rho0.
-__global__ __launch_bounds__(64) void setup_inv_kernel(SetupArgs a)
+template <bool KEEP>
+__device__ __forceinline__ void setup_inv_body(const SetupArgs &a)
 {
     extern __shared__ double sm[];
     const int pl = blockIdx.x;
@@ -504,17 +553,22 @@ __global__ __launch_bounds__(64) void setup_inv_kernel(SetupArgs a)
     int *ctype = a.ctype + (size_t)pl * mc;
 
     MPCQ_STAMP(0);
-    for (int e = t; e < n * n; e += 64) {  // (osqp-eigen keeps the upper triangle of the Hessian)
-        const int i = e / n, j = e % n;
-        Ph[i * ld + j] = (i <= j) ? P[i * n + j] : P[j * n + i];
+    double cost = 1.0;
+    if constexpr (KEEP) {
+        load_kept_scaling(a, pl, t, n, m, ld, out, Lo, Ph, Ah, Dv, Ev, Et);
+    } else {
+        for (int e = t; e < n * n; e += 64) {  // (osqp-eigen keeps the upper triangle of the Hessian)
+            const int i = e / n, j = e % n;
+            Ph[i * ld + j] = (i <= j) ? P[i * n + j] : P[j * n + i];
+        }
+        for (int e = t; e < m * n; e += 64) Ah[(e / n) * ld + e % n] = A[e];
+        for (int j = t; j < n; j += 64) { qh[j] = q0[j]; Dv[j] = 1.0; }
+        for (int i = t; i < m; i += 64) Ev[i] = 1.0;
+        if (t == 0) sh[0] = 1.0;
+        __syncthreads();
+        MPCQ_STAMP(1);
+        cost = ruiz_and_types(a, pl, t, n, m, mc, ld, Ph, Ah, Dv, Ev, Dt, Et, qh, sh, ctype);
     }
-    for (int e = t; e < m * n; e += 64) Ah[(e / n) * ld + e % n] = A[e];
-    for (int j = t; j < n; j += 64) { qh[j] = q0[j]; Dv[j] = 1.0; }
-    for (int i = t; i < m; i += 64) Ev[i] = 1.0;
-    if (t == 0) sh[0] = 1.0;
-    __syncthreads();
-    MPCQ_STAMP(1);
-    const double cost = ruiz_and_types(a, pl, t, n, m, mc, ld, Ph, Ah, Dv, Ev, Dt, Et, qh, sh, ctype);
     MPCQ_STAMP(3);
 
     // ---- M(rho0) and its inverse
@@ -556,22 +610,69 @@ __global__ __launch_bounds__(64) void setup_inv_kernel(SetupArgs a)
     }
     for (int k = t; k < nc; k += 64) {
         out[Lo.lam + k] = 0.0;
-        out[Lo.D + k] = k < n ? Dv[k] : 1.0;
-        out[Lo.Dinv + k] = k < n ? 1.0 / Dv[k] : 1.0;
+        if constexpr (!KEEP) {
+            out[Lo.D + k] = k < n ? Dv[k] : 1.0;
+            out[Lo.Dinv + k] = k < n ? 1.0 / Dv[k] : 1.0;
+        }
     }
-    for (int i = t; i < mc; i += 64) {
-        out[Lo.E + i] = i < m ? Ev[i] : 1.0;
-        out[Lo.Einv + i] = i < m ? 1.0 / Ev[i] : 1.0;
-        out[Lo.rscale + i] = i < m ? Et[i] : 1.0;
+    if constexpr (!KEEP) {
+        for (int i = t; i < mc; i += 64) {
+            out[Lo.E + i] = i < m ? Ev[i] : 1.0;
+            out[Lo.Einv + i] = i < m ? 1.0 / Ev[i] : 1.0;
+            out[Lo.rscale + i] = i < m ? Et[i] : 1.0;
+        }
     }
     if (t == 0) {
-        out[Lo.cs] = cost;
-        out[Lo.cs + 1] = 1.0 / cost;
+        if constexpr (!KEEP) {
+            out[Lo.cs] = cost;
+            out[Lo.cs + 1] = 1.0 / cost;
+        }
         out[Lo.rho0] = rho;
         a.status[pl] = ok ? 0 : kNonCvx;
         if (!ok) atomicOr(a.flags, 1);
     }
     MPCQ_STAMP(8);
+}
+
+__global__ __launch_bounds__(64) void setup_inv_kernel(SetupArgs a) { setup_inv_body<false>(a); }
+// M(rho0) and its Gauss-Jordan inverse alone on new matrices under the kept scaling.
+__global__ __launch_bounds__(64) void setup_inv_keep_kernel(SetupArgs a) { setup_inv_body<true>(a); }
+
+// ---- what mpcq_update_P_A_device checks on the device (its one flag word carries the answers back)
+// Shared plant: flag 8 when some QP's scaled lower bound is not below -OSQP_INFTY * MIN_SCALING under the block's
+// E (the host rule of mpcq_update_lower_bound: l E < -INFTY MIN_SCALING, or l <= -1e300).
+__global__ __launch_bounds__(256) void lower_free_kernel(const double *l, const double *E, int m, size_t total, int *flags)
+{
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const double v = l[i];
+        if (!(v * E[i % m] < -kInfty * kMinScaling) && !(v <= -1e300)) bad = true;
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flags, 8);
+}
+// Flag 16 when rows n + j of A are not the negated rows j bit for bit (mpcq_setup's test for the paired loop).
+__global__ __launch_bounds__(256) void paired_kernel(const double *A, int nn, int *flags)
+{
+    bool bad = false;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < nn; i += gridDim.x * 256)
+        if (!(A[nn + i] == -A[i])) bad = true;
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flags, 16);
+}
+// A QP whose previous x or y holds a non-finite entry starts cold: its warm-state rows (x', z, y; `es` bytes
+// per element) are zeroed after the warm-start kernel has filled them.
+__global__ __launch_bounds__(64) void cold_nonfinite_kernel(const double *x, const double *y, int n, int m, int nc, int mc,
+                                                            int batch, int es, void *xs, void *zs, void *ys)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= batch) return;
+    bool fin = true;
+    for (int i = 0; i < n; i++) fin = fin && isfinite(x[(size_t)b * n + i]);
+    for (int j = 0; j < m; j++) fin = fin && isfinite(y[(size_t)b * m + j]);
+    if (fin) return;
+    const int wx = nc * es / 4, wz = mc * es / 4;  // 32-bit words per row
+    unsigned *px = (unsigned *)xs + (size_t)b * wx, *pz = (unsigned *)zs + (size_t)b * wz, *py = (unsigned *)ys + (size_t)b * wz;
+    for (int i = 0; i < wx; i++) px[i] = 0u;
+    for (int j = 0; j < wz; j++) { pz[j] = 0u; py[j] = 0u; }
 }
 
 }  // namespace mpcq
@@ -581,6 +682,39 @@ extern "C" int mpcq_internal_setup_inv_launch(const mpcq::SetupArgs *args, hipSt
     if (args->n < 1 || args->n > 32 || args->m > 64) return -1;
     const size_t lds = 8 * mpcq::SetupWaveShape::make(args->n, args->m).total;
     hipLaunchKernelGGL(mpcq::setup_inv_kernel, dim3(args->n_plants), dim3(64), lds, stream, *args);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// The keep-scaling kernels (mpcq_update_P_A_device, rescale = 0): `inv` selects the direct-inverse reading.
+extern "C" int mpcq_internal_setup_keep_launch(const mpcq::SetupArgs *args, int inv, hipStream_t stream)
+{
+    const size_t lds = mpcq_internal_setup_wave_lds(args->n, args->m);
+    if (!lds || lds > 65536) return -1;
+    if (inv) hipLaunchKernelGGL(mpcq::setup_inv_keep_kernel, dim3(args->n_plants), dim3(64), lds, stream, *args);
+    else hipLaunchKernelGGL(mpcq::setup_wave_keep_kernel, dim3(args->n_plants), dim3(64), lds, stream, *args);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int mpcq_internal_lower_free_check(const double *l, const double *E, int m, size_t total, int *flags,
+                                              hipStream_t stream)
+{
+    if (!total) return 0;
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 1024);
+    hipLaunchKernelGGL(mpcq::lower_free_kernel, dim3(grid), dim3(256), 0, stream, l, E, m, total, flags);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int mpcq_internal_paired_check(const double *A, int nn, int *flags, hipStream_t stream)
+{
+    hipLaunchKernelGGL(mpcq::paired_kernel, dim3(std::min((nn + 255) / 256, 64)), dim3(256), 0, stream, A, nn, flags);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int mpcq_internal_cold_nonfinite(const double *x, const double *y, int n, int m, int nc, int mc, int batch,
+                                            int is_f32, void *xs, void *zs, void *ys, hipStream_t stream)
+{
+    hipLaunchKernelGGL(mpcq::cold_nonfinite_kernel, dim3((batch + 63) / 64), dim3(64), 0, stream, x, y, n, m, nc, mc,
+                       batch, is_f32 ? 4 : 8, xs, zs, ys);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -96,11 +96,18 @@ class _QpSolution(torch.autograd.Function):
                 raise ValueError(f"qp_solution: {name} must be a device fp64 tensor of shape {shape}")
         host = lambda t: t.detach().cpu().numpy()
         lh, uh, kp = host(l), host(u), solver.n_plants
-        if setup:  # (each plant's first QP supplies the setup's bounds; every QP's own follow below)
+        stream = torch.cuda.current_stream(q.device).cuda_stream
+        if isinstance(setup, str):  # (new matrices from the tensors' own memory, warm-started: mpcq_update_P_A_device)
+            if setup not in ("update", "update_keep"):
+                raise ValueError(f"qp_solution: setup={setup!r}: True, False, 'update' or 'update_keep'")
+            Pc, Ac = P.detach().contiguous(), A.detach().contiguous()
+            solver.update_P_A_device(Pc.data_ptr(), Ac.data_ptr(), 0 if setup == "update_keep" else 1, stream)
+            ctx.keep = (Pc, Ac)  # (alive until the copies enqueued on the stream have run)
+        elif setup:  # (each plant's first QP supplies the setup's bounds; every QP's own follow below)
             solver.setup(host(P), torch.zeros(kp, n, dtype=torch.float64).numpy(), host(A), lh[:kp], uh[:kp])
         solver.update_lin_cost(host(q))
         solver.update_bounds(lh, uh)
-        solver.solve(torch.cuda.current_stream(q.device).cuda_stream)
+        solver.solve(stream)
         view = solver.device_view()  # (publishes x and status on the same stream)
         x =torch.as_tensor(_DevArray(view["x"], (B, n), "<f8"), device=q.device).clone()
         status = torch.as_tensor(_DevArray(view["status"], (B,), "<i4"), device=q.device).clone()
@@ -231,7 +238,10 @@ def qp_solution(solver, P, A, q, l, u, setup=True):
 
     Forward: ``solver.setup(P, 0, A, l0, u0)`` with each plant's first QP's bounds, then ``update_lin_cost``,
     ``update_bounds`` and ``solve`` (host-side data updates).  With ``setup=False`` the caller vouches that the
-    solver already holds P and A, and only q, l, u are updated.  Backward is one
+    solver already holds P and A, and only q, l, u are updated.  ``setup="update"`` and ``setup="update_keep"`` hand
+    P and A to a solver that is already set up through ``update_P_A_device`` on the tensors' own memory (no host
+    copy of the matrices), equilibrated again or with the last setup's scaling kept (n <= 32, m <= 64): the QPs
+    are warm-started from the previous solve's (x, y).  Backward is one
     ``BatchSolver.sensitivity_data_device`` call: the gradient with respect to P is that of a
     symmetric P (``setup`` reads the upper triangle: a caller who parametrises that takes gP[i, j] + gP[j, i]);
     a shared plant's gP, gA are the sums over the batch.  ``backward`` must run before the solver solves again.
