@@ -490,6 +490,45 @@ int mpcq_mimo_setup_plants_device(mpcq_ctx *ctx, int nx, int nu, int ny, int s_r
 int mpcq_mimo_step_device(mpcq_ctx *ctx, const double *X_dev, double *U_dev, const double *yref_dev,
                           void *stream);
 
+/* ---- active-set sensitivities of the last MIMO step --------------------------------
+ * The definition of mpcq_sensitivity_device above, applied to the last mpcq_mimo_step_device of the context:
+ * the active rows by the polish rule on the step's final scaled iterate with u^ = E u of the step's bounds
+ * (l = -DBL_MAX: no row is lower-active, so there is no gl), and for each right-hand side r < n_rhs
+ * (1 <= n_rhs <= 4)  K [v; w] = [g_r; 0],  K = [P, A_a'; A_a, 0]:
+ *   gq_r = -v                                   (batch*n_rhs*n, QP-major, then r)
+ *   gu_r[i] = w_k where row i is the k-th active row, else 0   (batch*n_rhs*m)
+ * g_dev: batch*n_rhs*n cotangents (device, fp64), or NULL for g_r = e_r, the r-th component of the applied move
+ * x*[0:n_u] (then n_rhs <= n_u).  Solved in the scaled space with settings.delta and
+ * settings.polish_refine_iter, one factorisation per QP for all right-hand sides; the contract is the solution
+ * of the unregularised system.  n_active (batch): the active rows.  A QP that did not end MPCQ_SOLVED, whose
+ * reduced system could not be factored, or with more than n active rows (some bound pair j, n + j both active)
+ * gets all-zero outputs and n_active = -1.  Each output may be NULL, not all.
+ * Read-only on the context: a step after the call is bit-identical to the same step without it.  The kernel
+ * runs on `stream`, ordered after the context's last stream (an event), and the context's next step is ordered
+ * after it.  No atomics: two calls give identical bits.
+ * MPCQ_ERR_ORDER: no successful mpcq_mimo_setup_plants_device; no mpcq_mimo_step_device since the last setup.
+ * MPCQ_ERR_ARG: n_rhs out of range; NULL g with n_rhs > n_u; every output NULL; `stream` under graph capture
+ * (nothing is recorded into the capture).  A refused call writes nothing. */
+int mpcq_mimo_sensitivity_device(mpcq_ctx *ctx, const double *g_dev, int n_rhs, double *gq_dev, double *gu_dev,
+                                 int *n_active_dev, void *stream);
+/* Host-memory form (copies in/out, synchronises); the same arrays on the host. */
+int mpcq_mimo_sensitivity(mpcq_ctx *ctx, const double *g, int n_rhs, double *gq, double *gu, int *n_active);
+/* The same solve followed by the chain rule through the MIMO front end, q = Fx X + Fu U + Fr (1_N (x) yref) and
+ * u = W0 + Sbar X + Ku U: with gu_r = [gt; gb] split into horizon blocks of n_u, per right-hand side
+ *   dX = Fx' gq + K' sum_{k < min(s_rows, N)} (gt_k - gb_k)   (batch*n_rhs*n_x)
+ *   dU = Fu' gq + K0' sum_k (gb_k - gt_k)                     (batch*n_rhs*n_u)
+ *   dyref = Frs' gq                                           (batch*n_rhs*n_y)
+ * from the plant's own operator block, fp64 sums in ascending row index.  dyref is per QP: yref is one vector
+ * for the whole batch, so a caller who wants its gradient sums dyref over the QPs.  Each output may be NULL, not
+ * all.  Otherwise as mpcq_mimo_sensitivity_device. */
+int mpcq_mimo_step_vjp_device(mpcq_ctx *ctx, const double *g_dev, int n_rhs, double *dX_dev, double *dU_dev,
+                              double *dyref_dev, int *n_active_dev, void *stream);
+/* Step gains: mpcq_mimo_step_vjp_device with g = NULL and n_rhs = n_u, the gradients of the applied move
+ * x*[0:n_u] with respect to the step's X, previous U and yref at the current active set: the explicit-MPC
+ * feedback gain.  (U_new = U + x*[0:n_u] adds the identity to dU.) */
+int mpcq_mimo_step_gains_device(mpcq_ctx *ctx, double *dX_dev, double *dU_dev, double *dyref_dev, int *n_active_dev,
+                                void *stream);
+
 /* Last HIP error string of this thread (static storage). */
 const char *mpcq_last_error(void);
 

@@ -463,7 +463,7 @@ class BatchSolver:
         ptrs = [C.c_void_p(p) for p in (Ad_ptr, Bd_ptr, Cd_ptr, Q_ptr, R_ptr, RD_ptr, K_ptr, K0_ptr, w0_ptr)]
         _capi.check(lib().mpcq_mimo_setup_plants_device(self._ctx, int(nx), int(nu), int(ny), int(s_rows), *ptrs,
                                                         C.c_void_p(stream or 0)), "mpcq_mimo_setup_plants_device")
-        self.nx, self.nu = int(nx), int(nu)
+        self.nx, self.nu, self.ny = int(nx), int(nu), int(ny)
 
     def mimo_step_device(self, X_ptr: int, U_ptr: int, yref_ptr: int = 0, stream: int | None = None) -> None:
         """One controllerStep for every QP on device-resident X (batch, nx), U (batch, nu); asynchronous."""
@@ -471,6 +471,70 @@ class BatchSolver:
         _capi.check(lib().mpcq_mimo_step_device(self._ctx, C.c_void_p(X_ptr), C.c_void_p(U_ptr),
                                                 C.c_void_p(yref_ptr or 0), C.c_void_p(stream or 0)),
                     "mpcq_mimo_step_device")
+
+    # -- active-set sensitivities of the last MIMO step (mpcq_mimo_sensitivity*, mpcq_mimo_step_*)
+    def mimo_sensitivity(self, g=None, n_rhs: int | None = None):
+        """(gq, gu, n_active) of the last ``mimo_step_device``: ``g`` of shape (batch, n_rhs, n) (or (batch, n) for one
+        right-hand side) holds the cotangents dL/dx; None stands for e_r, r < n_rhs (default n_u): the components
+        of the applied move x[0:n_u].  gq (batch, n_rhs, n), gu (batch, n_rhs, m), n_active (batch), -1 (and zero
+        gradients) where the QP did not end SOLVED."""
+        gp = None
+        if g is not None:
+            g = _c64(g)
+            if g.ndim == 2:
+                g = g[:, None, :]
+            n_rhs = g.shape[1] if n_rhs is None else int(n_rhs)
+            g = np.ascontiguousarray(g.reshape(self.batch, n_rhs, self.n))
+            gp = _dp(g)
+        elif n_rhs is None:
+            n_rhs = self.nu
+        n_rhs = int(n_rhs)
+        gq, gu = np.empty((self.batch, max(n_rhs, 0), self.n)), np.empty((self.batch, max(n_rhs, 0), self.m))
+        na = np.empty(self.batch, dtype=np.int32)
+        _capi.check(lib().mpcq_mimo_sensitivity(self._ctx, gp, n_rhs, _dp(gq), _dp(gu),
+                                                na.ctypes.data_as(C.POINTER(C.c_int))), "mpcq_mimo_sensitivity")
+        return gq, gu, na
+
+    def mimo_sensitivity_device(self, g_ptr: int = 0, n_rhs: int = 1, gq_ptr: int = 0, gu_ptr: int = 0,
+                                n_active_ptr: int = 0, stream: int | None = None) -> None:
+        """Same on device-resident buffers (fp64; n_active int32); g_ptr 0: g_r = e_r; any output may be 0, not
+        all.  Asynchronous on ``stream``, ordered after the solver's last stream."""
+        _capi.check(lib().mpcq_mimo_sensitivity_device(self._ctx, C.c_void_p(g_ptr or 0), int(n_rhs),
+                                                       C.c_void_p(gq_ptr or 0), C.c_void_p(gu_ptr or 0),
+                                                       C.c_void_p(n_active_ptr or 0), C.c_void_p(stream or 0)),
+                    "mpcq_mimo_sensitivity_device")
+
+    def mimo_step_vjp_device(self, g_ptr: int = 0, n_rhs: int = 1, dX_ptr: int = 0, dU_ptr: int = 0,
+                             dyref_ptr: int = 0, n_active_ptr: int = 0, stream: int | None = None) -> None:
+        """The vector-Jacobian products of the last MIMO step with respect to X (batch, n_rhs, nx), U
+        (batch, n_rhs, nu) and yref (batch, n_rhs, ny; per QP) for the cotangents at g_ptr (batch, n_rhs, n), on
+        device-resident buffers; asynchronous on ``stream``."""
+        ptrs = [C.c_void_p(p or 0) for p in (dX_ptr, dU_ptr, dyref_ptr, n_active_ptr)]
+        _capi.check(lib().mpcq_mimo_step_vjp_device(self._ctx, C.c_void_p(g_ptr or 0), int(n_rhs), *ptrs,
+                                                    C.c_void_p(stream or 0)), "mpcq_mimo_step_vjp_device")
+
+    def mimo_step_gains_device(self, dX_ptr: int = 0, dU_ptr: int = 0, dyref_ptr: int = 0, n_active_ptr: int = 0,
+                               stream: int | None = None) -> None:
+        """The gradients of the applied move x[0:n_u] (``mimo_step_vjp_device`` with g = e_r, n_rhs = n_u) on
+        device-resident buffers; asynchronous on ``stream``."""
+        ptrs = [C.c_void_p(p or 0) for p in (dX_ptr, dU_ptr, dyref_ptr, n_active_ptr)]
+        _capi.check(lib().mpcq_mimo_step_gains_device(self._ctx, *ptrs, C.c_void_p(stream or 0)),
+                    "mpcq_mimo_step_gains_device")
+
+    def mimo_step_gains(self):
+        """(dX, dU, dyref, n_active) of the last MIMO step as numpy arrays: the gradient of component r of the
+        applied move with respect to X (batch, nu, nx), the previous U (batch, nu, nu) and yref (batch, nu, ny; per
+        QP) at the current active set."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)
+        dX, dU, dy = new(self.batch, self.nu, self.nx), new(self.batch, self.nu, self.nu), new(self.batch, self.nu, self.ny)
+        na = torch.empty(self.batch, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        self.mimo_step_gains_device(dX.data_ptr(), dU.data_ptr(), dy.data_ptr(), na.data_ptr(), stream.cuda_stream)
+        stream.synchronize()
+        return dX.cpu().numpy(), dU.cpu().numpy(), dy.cpu().numpy(), na.cpu().numpy()
 
     def mpc_step_device(self, X_ptr: int, U_ptr: int, xref: float = 0.0, stream: int | None = None) -> None:
         """Same on device-resident fp64 buffers (e.g. torch tensors' data_ptr()); asynchronous."""

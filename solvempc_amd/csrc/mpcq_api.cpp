@@ -168,6 +168,7 @@ struct mpcq_ctx {
     double *d_mimo = nullptr;
     int mimo_N = 0, mimo_nx = 0, mimo_nu = 0, mimo_ny = 0, mimo_srows = 0, mimo_diag_k0 = 0;
     bool mimo_only = false;  // n > 32 or m > 64 per plant: only the MIMO entry points serve it
+    bool mimo_stepped = false;  // a mpcq_mimo_step_device since the last MIMO setup (mpcq_mimo_sensitivity* needs one)
     // receding-horizon stream counters (mpcq_mpc_run_device): per-QP iterations and unsolved steps
     int *d_it_acc = nullptr, *d_uns_acc = nullptr;
     bool stream_acc = false;  // launches made inside mpcq_mpc_run_device accumulate into them
@@ -2828,6 +2829,7 @@ int mpcq_mimo_setup_plants_device(mpcq_ctx *c, int nx, int nu, int ny, int s_row
     c->mimo_N = N; c->mimo_nx = nx; c->mimo_nu = nu; c->mimo_ny = ny; c->mimo_srows = s_rows;
     c->mode = mpcq_ctx::Mode::None;
     c->sens_ok = false;
+    c->mimo_stepped = false;
     c->gen++;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(c->d_flags, 0, 4, s));
@@ -2915,7 +2917,118 @@ int mpcq_mimo_step_device(mpcq_ctx *c, const double *X, double *U, const double 
     }
     c->last = s;
     c->fresh = false;
+    c->mimo_stepped = true;
     return MPCQ_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The refusals of include/mpcq.h for the MIMO sensitivity calls, before anything is enqueued or written
+int mimo_sens_check(mpcq_ctx *c, const char *fn, bool implicit_g, int n_rhs, bool any_out, hipStream_t s)
+{
+    int rc = check_ctx(c, kNone);
+    if (rc) return rc;
+    if (c->mode != mpcq_ctx::Mode::Mimo)
+        return fail(MPCQ_ERR_ORDER, std::string(fn) + ": mpcq_mimo_setup_plants_device has not succeeded");
+    if (!c->mimo_stepped)
+        return fail(MPCQ_ERR_ORDER, std::string(fn) + ": needs a mpcq_mimo_step_device since the last setup");
+    if (n_rhs < 1 || n_rhs > 4) return fail(MPCQ_ERR_ARG, std::string(fn) + ": 1 <= n_rhs <= 4");
+    if (implicit_g && n_rhs > c->mimo_nu)
+        return fail(MPCQ_ERR_ARG, std::string(fn) + ": g == NULL stands for the applied move's components, n_rhs <= n_u");
+    if (!any_out) return fail(MPCQ_ERR_ARG, std::string(fn) + ": every output is NULL");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return fail(MPCQ_ERR_ARG, std::string(fn) + ": the stream is under graph capture");
+    }
+    return MPCQ_OK;
+}
+
+// The kernel on s, ordered after the context's last stream; the context's next launches ordered after it.
+int mimo_sens_enqueue(mpcq_ctx *c, const double *g, int n_rhs, double *gq, double *gu, double *dX, double *dU,
+                      double *dyref, int *nact, hipStream_t s)
+{
+    if (s != c->last) {
+        if (!c->sens_ev) HIPCHK(hipEventCreateWithFlags(&c->sens_ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->sens_ev, c->last));
+        HIPCHK(hipStreamWaitEvent(s, c->sens_ev, 0));
+    }
+    mpcq::MimoSensArgs a{};
+    a.batch = c->dims.batch;
+    a.N = c->mimo_N; a.nx = c->mimo_nx; a.nu = c->mimo_nu; a.ny = c->mimo_ny; a.s_rows = c->mimo_srows;
+    a.n_rhs = n_rhs;
+    a.ops_stride = (size_t)mpcq::MimoLayout::make(a.N, a.nx, a.nu, a.ny).total;
+    a.ops = c->d_mimo;
+    a.u = c->d_u;
+    a.zs = (const double *)c->d_zs;
+    a.ys = (const double *)c->d_ys;
+    a.status = c->d_status;
+    a.g = g;
+    a.gq = gq; a.gu = gu;
+    a.dX = dX; a.dU = dU; a.dyref = dyref;
+    a.n_active = nact;
+    a.delta = c->set.delta;
+    a.refine = c->set.polish_refine_iter;
+    hipError_t err = hipSuccess;
+    const int lr = mpcq_internal_mimo_sens_launch(&a, c->cus, s, &err);
+    if (lr == -1) return fail(MPCQ_ERR_ARG, "mimo sensitivity: shape beyond the kernel's capacity");
+    if (lr) return fail(MPCQ_ERR_HIP, std::string("mimo sensitivity kernel launch failed: ") + hipGetErrorString(err));
+    if (s != c->last) {
+        HIPCHK(hipEventRecord(c->sens_ev, s));
+        HIPCHK(hipStreamWaitEvent(c->last, c->sens_ev, 0));
+    }
+    return MPCQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpcq_mimo_sensitivity_device(mpcq_ctx *c, const double *g, int n_rhs, double *gq, double *gu, int *n_active,
+                                 void *stream)
+{
+    int rc = mimo_sens_check(c, "mpcq_mimo_sensitivity_device", !g, n_rhs, gq || gu || n_active, (hipStream_t)stream);
+    if (rc) return rc;
+    return mimo_sens_enqueue(c, g, n_rhs, gq, gu, nullptr, nullptr, nullptr, n_active, (hipStream_t)stream);
+}
+
+int mpcq_mimo_sensitivity(mpcq_ctx *c, const double *g, int n_rhs, double *gq, double *gu, int *n_active)
+{
+    int rc = mimo_sens_check(c, "mpcq_mimo_sensitivity", !g, n_rhs, gq || gu || n_active, c ? c->last : nullptr);
+    if (rc) return rc;
+    const size_t B = c->dims.batch, n = c->dims.n, m = c->dims.m, R = (size_t)n_rhs;
+    // staging of this call alone: g and gq (B R n each), gu (B R m), then B ints
+    double *d = nullptr;
+    if (hipMalloc((void **)&d, 8 * (B * R * (2 * n + m) + (B + 1) / 2)) != hipSuccess)
+        return fail(MPCQ_ERR_HIP, "hipMalloc failed (mimo sensitivity staging)");
+    double *dg = d, *dgq = dg + B * R * n, *dgu = dgq + B * R * n;
+    int *dna = (int *)(dgu + B * R * m);
+    rc = g ? h2d(dg, g, 8 * B * R * n, c->last) : MPCQ_OK;
+    if (!rc) rc = mimo_sens_enqueue(c, g ? dg : nullptr, n_rhs, dgq, dgu, nullptr, nullptr, nullptr, dna, c->last);
+    if (!rc && !(rc = d2h(c, gq, dgq, 8 * B * R * n)) && !(rc = d2h(c, gu, dgu, 8 * B * R * m)))
+        rc = d2h(c, n_active, dna, 4 * B);
+    (void)hipStreamSynchronize(c->last);
+    (void)hipFree(d);
+    return rc;
+}
+
+int mpcq_mimo_step_vjp_device(mpcq_ctx *c, const double *g, int n_rhs, double *dX, double *dU, double *dyref,
+                              int *n_active, void *stream)
+{
+    int rc = mimo_sens_check(c, "mpcq_mimo_step_vjp_device", !g, n_rhs, dX || dU || dyref || n_active,
+                             (hipStream_t)stream);
+    if (rc) return rc;
+    return mimo_sens_enqueue(c, g, n_rhs, nullptr, nullptr, dX, dU, dyref, n_active, (hipStream_t)stream);
+}
+
+int mpcq_mimo_step_gains_device(mpcq_ctx *c, double *dX, double *dU, double *dyref, int *n_active, void *stream)
+{
+    int rc = mimo_sens_check(c, "mpcq_mimo_step_gains_device", true, c ? std::max(c->mimo_nu, 1) : 1,
+                             dX || dU || dyref || n_active, (hipStream_t)stream);
+    if (rc) return rc;
+    return mimo_sens_enqueue(c, nullptr, c->mimo_nu, nullptr, nullptr, dX, dU, dyref, n_active, (hipStream_t)stream);
 }
 
 }  // extern "C"

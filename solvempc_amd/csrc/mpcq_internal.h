@@ -420,6 +420,24 @@ struct MimoArgs {
     double *rho_out;
     long long *stamps;          // debug (MPCQ_MIMO_STAMPS) or null
 };
+
+// Arguments of mimo_sens_kernel (mpcq_mimo_sens.hip): the active-set sensitivities of the last MIMO step and the
+// front end's chain rule, one workgroup per QP, fp64.  Everything of the context is read-only.
+struct MimoSensArgs {
+    int batch, N, nx, nu, ny, s_rows;
+    int n_rhs;                  // right-hand sides per QP (1..4), one factorisation for all of them
+    size_t ops_stride;
+    const double *ops;          // [plant] MimoLayout
+    const double *u;            // [batch] 2n: the step's unscaled upper bounds (MimoArgs::u_out)
+    const double *zs, *ys;      // [batch] 2n: the step's final scaled iterate
+    const int *status;          // [batch] only MPCQ_SOLVED QPs get a sensitivity
+    const double *g;            // [batch][n_rhs] n: the cotangents, or null: e_r for right-hand side r
+    double *gq, *gu;            // [batch][n_rhs] n, 2n (each may be null)
+    double *dX, *dU, *dyref;    // [batch][n_rhs] nx, nu, ny: the chain rule on (gq, gu) (each may be null)
+    int *n_active;              // [batch] rows of the reduced system, -1 where no sensitivity exists (or null)
+    double delta;
+    int refine;
+};
 }  // namespace mpcq
 
 namespace mpcq {
@@ -706,6 +724,11 @@ int mpcq_internal_order_info(int batch, const int *list, const int *slot, int *s
 // (one 512-thread workgroup per QP: KKT inverse by Gauss-Jordan in VGPRs, structured A).
 int mpcq_internal_mimo_setup_launch(const mpcq::MimoSetupArgs *a, hipStream_t s);
 int mpcq_internal_mimo_solve_launch(const mpcq::MimoArgs *a, hipStream_t s);
+// Sensitivities of the last MIMO step with the chain rule as the kernel's tail (mpcq_mimo_sens.hip; every shape
+// the MIMO setup accepts): 0 launched, -1 unsupported shape or n_rhs, -2 HIP error (*err).  The workgroup's
+// dynamic LDS bytes for n variables: mpcq_internal_mimo_sens_lds.
+int mpcq_internal_mimo_sens_launch(const mpcq::MimoSensArgs *a, int cus, hipStream_t s, hipError_t *err);
+size_t mpcq_internal_mimo_sens_lds(int n);
 // One pass per batch of distinct SISO plants (mpcq_plant.hip): condensing + setup + one
 // controllerStep per plant, two plants per wave.  0 launched, -1 unsupported shape, -2 HIP error.
 int mpcq_internal_plant_step_launch(const mpcq::PlantStepArgs *a, int is_f32, hipStream_t s);

@@ -15,12 +15,15 @@ torch.
 ``mpc_plant_solution`` is the MPC step as a function of the plant model and the cost weights themselves: the
 condensing and the setup run on the device from the plant tensors (``BatchSolver.mpc_setup_plants_device``), and
 the backward pass chains ``sensitivity_data_device`` with the condensing's vector-Jacobian product
-(``solvempc_amd.condense_vjp_device``, solvempc_amd/csrc/mpcq_condense_vjp.hip)."""
+(``solvempc_amd.condense_vjp_device``, solvempc_amd/csrc/mpcq_condense_vjp.hip).
+
+``mimo_solution`` is the MIMO step (``BatchSolver.mimo_step_device``; n up to 128) as a function of X, U and yref:
+its backward pass is ``BatchSolver.mimo_step_vjp_device`` (solvempc_amd/csrc/mpcq_mimo_sens.hip)."""
 from __future__ import annotations
 
 import torch
 
-__all__ = ["mpc_solution", "qp_solution", "mpc_plant_solution"]
+__all__ = ["mpc_solution", "qp_solution", "mpc_plant_solution", "mimo_solution"]
 
 
 class _DevArray:
@@ -131,6 +134,42 @@ class _QpSolution(torch.autograd.Function):
         return None, gP, gA, gq, gl, gu, None
 
 
+class _MimoSolution(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, X, U, yref):
+        B, n = solver.batch, solver.n
+        nx, nu, ny = solver.nx, getattr(solver, "nu", 0), getattr(solver, "ny", 0)
+        if not (nu and ny):
+            raise RuntimeError("mimo_solution: the solver has no MIMO plants (BatchSolver.mimo_setup_plants_device)")
+        for name, t, shape in (("X", X, (B, nx)), ("U", U, (B, nu)), ("yref", yref, (ny,))):
+            if not (t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == shape):
+                raise ValueError(f"mimo_solution: {name} must be a device fp64 tensor of shape {shape}")
+        Xc, Uc, yc = X.detach().contiguous(), U.detach().clone().contiguous(), yref.detach().contiguous()
+        stream = torch.cuda.current_stream(X.device).cuda_stream
+        solver.mimo_step_device(Xc.data_ptr(), Uc.data_ptr(), yc.data_ptr(), stream)
+        view = solver.device_view()
+        x = torch.as_tensor(_DevArray(view["x"], (B, n), "<f8"), device=X.device).clone()
+        status = torch.as_tensor(_DevArray(view["status"], (B,), "<i4"), device=X.device).clone()
+        ctx.keep = (Xc, Uc, yc)
+        ctx.solver, ctx.count, ctx.dims = solver, solver.solve_count, (nx, nu, ny)
+        ctx.mark_non_differentiable(status)
+        return x, status
+
+    @staticmethod
+    def backward(ctx, gx, _gstatus):
+        solver = ctx.solver
+        if solver.solve_count != ctx.count:
+            raise RuntimeError("mimo_solution.backward: the solver has solved again since this forward pass, so its "
+                               "state is no longer this solve's; run backward before the next solve")
+        B, (nx, nu, ny) = solver.batch, ctx.dims
+        g = gx.contiguous()
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=g.device)
+        dX, dU, dy = new(B, nx), new(B, nu), new(B, ny)
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        solver.mimo_step_vjp_device(g.data_ptr(), 1, dX.data_ptr(), dU.data_ptr(), dy.data_ptr(), 0, stream)
+        return None, dX, dU, dy.sum(dim=0)  # (yref is one vector for the whole batch)
+
+
 _PLANT = ("Ad", "Bd", "Cd", "K", "Q", "R", "RD")
 
 
@@ -229,6 +268,17 @@ def mpc_plant_solution(solver, Ad, Bd, Cd, K, Q, R, RD, X, U, ref, s_rows=10, se
     operators, which are then fetched once per forward pass through the host (``solvempc_amd.condense``), only when
     one of the three requires a gradient.  ``backward`` must run before the solver solves again."""
     return _MpcPlantSolution.apply(solver, s_rows, setup, Ad, Bd, Cd, K, Q, R, RD, X, U, ref)
+
+
+def mimo_solution(solver, X, U, yref):
+    """One MIMO MPC step ``solver.mimo_step_device`` (after ``mimo_setup_plants_device``) on device fp64 tensors
+    X (batch, nx), U (batch, nu), yref (ny,), differentiable with respect to all three.  Returns ``(x, status)`` as
+    ``mpc_solution`` does; the caller's U is left alone (the applied move is x[:, :nu]).  Backward is one
+    ``BatchSolver.mimo_step_vjp_device`` call on the incoming cotangent (solvempc_amd/csrc/mpcq_mimo_sens.hip;
+    DESIGN.md 4.15), the per-QP gradients of yref summed over the batch: the gradient of the QP's optimum at the
+    active set of the step's final iterate, zero for a QP that did not end SOLVED.  ``backward`` must run before
+    the solver solves again."""
+    return _MimoSolution.apply(solver, X, U, yref)
 
 
 def qp_solution(solver, P, A, q, l, u, setup=True):
