@@ -285,7 +285,7 @@ struct AdmmArgs {
     T eps10[4];
     // a hardest-first solve in one launch: the finalize stores (status, iter) of list slot i at
     // info_slot[2 i], [2 i + 1], one 8-B store per QP into the wave's own 128-B line, instead of two
-    // scattered 4-B stores at the QP's index (mpcq_api.cpp materialize_info permutes them when read); null:
+    // scattered 4-B stores at the QP's index (mpcq_host_context.cpp materialize_info permutes them when read); null:
     // at the QP's index in status, iter
     int *info_slot;
 };
@@ -537,7 +537,7 @@ struct SensChainArgs {
 // variant a call needs is decided here and nowhere else:
 //     a reference with data (ref && ref->p): Ref;  a record (lg): Log;  both: RefLog;  neither: Scalar
 // (a null or empty reference never reaches a REF unit).  The callers pass the reference only where the kernel's
-// front end reads it (mpcq_api.cpp).  Return codes: 0 launched, -1 the variant or the shape (capacity, (KN, KM),
+// front end reads it (mpcq_host_solve.cpp).  Return codes: 0 launched, -1 the variant or the shape (capacity, (KN, KM),
 // the tile stream's paired condensed-MPC shape) is not compiled, -2 HIP error.
 namespace mpcq {
 enum class Variant { Scalar, Ref, Log, RefLog };

@@ -16,7 +16,7 @@
 //
 // For an MPC step q = Fx X + Fu U + Fr 1 xref and u = W0 + Sbar X + Ku U (setF :372-375, setUpperBound
 // :360-369) are affine in (X, U, xref), and so is v_j: the host folds -A P^-1 [Fx Fu Fr1] - [Sbar Ku 0]
-// into one m x (nx + 3) map once per operator set (mpcq_api.cpp build_order_map), and the key costs
+// into one m x (nx + 3) map once per operator set (mpcq_host_setup.cpp build_order_map), and the key costs
 // m (nx + 2) fp64 FMAs per QP here.
 //
 // A counting sort in two launches: order_key_kernel bins the keys (OrderBins::bin: 16 bins per octave of

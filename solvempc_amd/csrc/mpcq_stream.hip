@@ -53,7 +53,7 @@ extern "C" int mpcq_internal_tick(long long *step, hipStream_t s)
 
 // The QP data a controllerStep leaves in the solver (OSQP's q and u after updateGradient /
 // updateUpperBound, :96-99), computed from the step's saved X and U when a caller first reads them
-// (mpcq_api.cpp materialize_qu): the tile path's phase 0 saves X, U instead of writing the 480 B/QP
+// (mpcq_host_context.cpp materialize_qu): the tile path's phase 0 saves X, U instead of writing the 480 B/QP
 // fp64 q, u.  The arithmetic is the tile kernel prologue's, operation for operation (fp64, no
 // contraction): q = Fx X + Fu U + (Fr 1 xref), u = W0 + Sbar X + Ku U.
 namespace mpcq {

@@ -1017,7 +1017,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, O
                     o_status[b] = sta;
                     o_iter[b] = it - cst[gi];
                 }
-                if (a.rho_out) o_rho[b] = (double)rho[gi];  // (null: the fp64 rhos above is reported, mpcq_api.cpp
+                if (a.rho_out) o_rho[b] = (double)rho[gi];  // (null: the fp64 rhos above is reported, mpcq_host_context.cpp
                                                             // materialize_rho)
                 if (a.it_acc) {
                     a.it_acc[b] += it - cst[gi];
@@ -2118,7 +2118,7 @@ static int tile_stream_launch(const AdmmArgs<T> &a, hipStream_t s, const RefArgs
         if (a.paired && a.all_ineq && a.lower_free) {
             // (a stream is latency-bound: few waves.  Compiled for two waves per SIMD (its plant and check code
             // spill, outside the hot loop), or with StreamArgs::occ 1 for one: the whole register file, no
-            // spills, but slower (mpcq_api.cpp launch_tile_stream))
+            // spills, but slower (mpcq_host_mpc.cpp launch_tile_stream))
             constexpr int WPB = 4;
             const int waves = (a.batch + a.sim.cpw - 1) / a.sim.cpw;
             const dim3 grid((waves + WPB - 1) / WPB), block(64 * WPB);
@@ -2165,7 +2165,7 @@ static int tile_launch(const AdmmArgs<T> &a, hipStream_t s, const RefArgs *ref =
 }
 
 // Lazily published solution of a tile solve (osqp store_solution, read by getSolution :105 only when a
-// caller asks: mpcq_api.cpp materialize_xy).  The tile finalize stores the warm state x' (W-basis), z, y,
+// caller asks: mpcq_host_context.cpp materialize_xy).  The tile finalize stores the warm state x' (W-basis), z, y,
 // rho, status and U += x(0); x = D W x' and y = E y / c are formed here, for every QP, with the finalize's
 // own arithmetic (the same MFMA product of the same W image, the same roundings): bit for bit what an eager
 // finalize would have written.  One 16-QP column group per wave, index order.

@@ -1296,7 +1296,7 @@ def test_ordered_step_ragged_batch_and_snapshot(plant, dtype, monkeypatch):
 @pytest.mark.parametrize("dtype", ["f64", "mixed"])
 def test_ordered_step_lazy_info(plant, dtype, monkeypatch):
     """A hardest-first step in one launch stores (status, iter) in list-slot order, one 8-B store per QP
-    into its wave's line (AdmmArgs::info_slot), and mpcq_api.cpp materialize_info permutes them when read:
+    into its wave's line (AdmmArgs::info_slot), and mpcq_host_context.cpp materialize_info permutes them when read:
     bit-identical to the stores at the QPs' indices (MPCQ_LAZY_INFO=0) whichever reader comes first
     (get_info; get_solution, whose publish kernel reads the status; the device view), and a step that
     nobody read is superseded by the next one (10,001 QPs: a ragged last wave)."""

@@ -185,7 +185,7 @@ def test_full_config3_batch_every_plant(plant, dtype):
 
 @pytest.mark.parametrize("dtype,N,B", [("f32", 20, 3001), ("f64", 20, 3001), ("f64", 32, 500), ("f64", 15, 777)])
 def test_hardest_first_plants_are_transparent(plant, dtype, N, B, monkeypatch):
-    """The one-pass step runs its batch hardest-first (the first plant's order map, mpcq_api.cpp
+    """The one-pass step runs its batch hardest-first (the first plant's order map, mpcq_host_plants.cpp
     plants_order_map, and mpcq_order.hip's counting sort; slot i of the grid runs plant list[i]): every
     output bit-identical to index order (MPCQ_PLANT_ORDER=0) on a ragged batch, the list a permutation of
     it, and the plants that need the most iterations in its first part.  A second step with the same plant
