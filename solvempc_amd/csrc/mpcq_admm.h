@@ -23,18 +23,11 @@
 // every check_termination iterations: OSQP update_info / check_termination / adapt_rho.
 #pragma once
 #include "mpcq_internal.h"
+#include "mpcq_lane.h"
 
 #include <math.h>
 
 namespace mpcq {
-
-
-template <typename T> __device__ __forceinline__ T tfma(T a, T b, T c);
-template <> __device__ __forceinline__ float tfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-template <> __device__ __forceinline__ double tfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-template <typename T> __device__ __forceinline__ T tabs(T a) { return a < T(0) ? -a : a; }
-template <typename T> __device__ __forceinline__ T tmax(T a, T b) { return a > b ? a : b; }
-template <typename T> __device__ __forceinline__ T tmin(T a, T b) { return a < b ? a : b; }
 
 // ---------------------------------------------------------------------------------------------
 // Cold-path certificates (OSQP is_primal_infeasible / is_dual_infeasible).  They run only when a
@@ -49,18 +42,18 @@ __device__ bool primal_infeasible(const AdmmArgs<T> &a, const PlantOps<T> &op, c
         T d = a.ys[b * MC + j] - a.snap_y[b * MC + j];
         const T up = uh[j * 64], lo = lh ? lh[j * 64] : T(-kInfty);
         const bool uinf = up > T(kInfty * kMinScaling), linf = lo < T(-kInfty * kMinScaling);
-        if (uinf) d = linf ? T(0) : tmin(d, T(0));
-        else if (linf) d = tmax(d, T(0));
+        if (uinf) d = linf ? T(0) : tt_min(d, T(0));
+        else if (linf) d = tt_max(d, T(0));
         return d;
     };
     T ndy = 0, lhs = 0;
 #pragma unroll 1
     for (int j = 0; j < MC; j++) {
         const T d = dyj(j);
-        ndy = tmax(ndy, tabs(scaled ? d : op.E[j] * d));
+        ndy = tt_max(ndy, tt_abs(scaled ? d : op.E[j] * d));
         const T up = uh[j * 64], lo = lh ? lh[j * 64] : T(-kInfty);
-        if (up < T(kInfty * kMinScaling)) lhs += up * tmax(d, T(0));
-        if (lo > T(-kInfty * kMinScaling)) lhs += lo * tmin(d, T(0));
+        if (up < T(kInfty * kMinScaling)) lhs += up * tt_max(d, T(0));
+        if (lo > T(-kInfty * kMinScaling)) lhs += lo * tt_min(d, T(0));
     }
     if (!(ndy > T(kDivisionTol))) return false;
     if (!(lhs < eps * ndy)) return false;
@@ -69,8 +62,8 @@ __device__ bool primal_infeasible(const AdmmArgs<T> &a, const PlantOps<T> &op, c
     for (int k = 0; k < NC; k++) {
         T s = 0;
 #pragma unroll 1
-        for (int j = 0; j < MC; j++) s = tfma(op.Ah[j * NC + k], dyj(j), s);
-        nat = tmax(nat, tabs(scaled ? s : op.Dinv[k] * s));
+        for (int j = 0; j < MC; j++) s = tt_fma(op.Ah[j * NC + k], dyj(j), s);
+        nat = tt_max(nat, tt_abs(scaled ? s : op.Dinv[k] * s));
     }
     return nat < eps * ndy;
 }
@@ -82,15 +75,15 @@ __device__ bool dual_infeasible(const AdmmArgs<T> &a, const PlantOps<T> &op, con
     auto dxp = [&](int k) -> T { return a.xs[b * NC + k] - a.snap_x[b * NC + k]; };
     T qdx = 0;  // q^' dx^ = (W' q^)' dx'
 #pragma unroll 1
-    for (int k = 0; k < NC; k++) qdx = tfma(g[k * 64], dxp(k), qdx);
+    for (int k = 0; k < NC; k++) qdx = tt_fma(g[k * 64], dxp(k), qdx);
     if (!(qdx < T(0))) return false;  // necessary: ||D dx^|| >= 0
     T ndx = 0;
 #pragma unroll 1
     for (int i = 0; i < NC; i++) {
         T s = 0;
 #pragma unroll 1
-        for (int k = 0; k < NC; k++) s = tfma(op.W[i * NC + k], dxp(k), s);
-        ndx = tmax(ndx, tabs(scaled ? s : op.D[i] * s));
+        for (int k = 0; k < NC; k++) s = tt_fma(op.W[i * NC + k], dxp(k), s);
+        ndx = tt_max(ndx, tt_abs(scaled ? s : op.D[i] * s));
     }
     const T cs = scaled ? T(1) : op.cs[0];
     if (!(ndx > T(kDivisionTol))) return false;
@@ -100,15 +93,15 @@ __device__ bool dual_infeasible(const AdmmArgs<T> &a, const PlantOps<T> &op, con
     for (int i = 0; i < NC; i++) {
         T s = 0;
 #pragma unroll 1
-        for (int k = 0; k < NC; k++) s = tfma(op.PW[i * NC + k], dxp(k), s);
-        npdx = tmax(npdx, tabs(scaled ? s : op.Dinv[i] * s));
+        for (int k = 0; k < NC; k++) s = tt_fma(op.PW[i * NC + k], dxp(k), s);
+        npdx = tt_max(npdx, tt_abs(scaled ? s : op.Dinv[i] * s));
     }
     if (!(npdx < cs * eps * ndx)) return false;
 #pragma unroll 1
     for (int j = 0; j < MC; j++) {
         T s = 0;
 #pragma unroll 1
-        for (int k = 0; k < NC; k++) s = tfma(op.WtA[j * NC + k], dxp(k), s);
+        for (int k = 0; k < NC; k++) s = tt_fma(op.WtA[j * NC + k], dxp(k), s);
         if (!scaled) s *= op.Einv[j];
         const T up = uh[j * 64], lo = lh ? lh[j * 64] : T(-kInfty);
         if ((up < T(kInfty * kMinScaling) && s > eps * ndx) || (lo > T(-kInfty * kMinScaling) && s < -eps * ndx))
@@ -229,7 +222,7 @@ void MPCQ_LANE_KERNEL(AdmmArgs<T> a MPCQ_LANE_REF_PARAM)
         for (int k = 0; k < NC; k++) {  // g = W' q^
             T s = 0;
 #pragma unroll
-            for (int i = 0; i < NC; i++) s = tfma(op.W[i * NC + k], qh[i], s);
+            for (int i = 0; i < NC; i++) s = tt_fma(op.W[i * NC + k], qh[i], s);
             g[k * 64] = s;
         }
     }
@@ -306,22 +299,22 @@ void MPCQ_LANE_KERNEL(AdmmArgs<T> a MPCQ_LANE_REF_PARAM)
                 for (int i = 0; i < NC; i++) {
                     const T xv = xs[i];
 #pragma unroll
-                    for (int k = 0; k < NC; k++) xi[k] = tfma(sWtW[k * NC + i], xv, xi[k]);
+                    for (int k = 0; k < NC; k++) xi[k] = tt_fma(sWtW[k * NC + i], xv, xi[k]);
                 }
 #pragma unroll
                 for (int j = 0; j < MC; j++) {
                     T rj = rho;
                     if (!ALL_INEQ) rj = ctype[j] == -1 ? T(kRhoMin) : rho * base[L.rscale + j];
-                    const T w = tfma(rj, z[j], -y[j]);
+                    const T w = tt_fma(rj, z[j], -y[j]);
 #pragma unroll
-                    for (int k = 0; k < NC; k++) xi[k] = tfma(WtA[j * NC + k], w, xi[k]);
+                    for (int k = 0; k < NC; k++) xi[k] = tt_fma(WtA[j * NC + k], w, xi[k]);
                 }
             }
             // ---- eta = xi / (1 + rho lambda) ; x' = alpha eta + (1-alpha) x'
 #pragma unroll
             for (int k = 0; k < NC; k++) {
                 xi[k] = xi[k] * dk[k * 64];
-                xs[k] = tfma(alpha, xi[k], oma * xs[k]);
+                xs[k] = tt_fma(alpha, xi[k], oma * xs[k]);
             }
             // ---- rows: z~ = B eta ; relaxation ; projection ; dual update
             {
@@ -331,17 +324,17 @@ void MPCQ_LANE_KERNEL(AdmmArgs<T> a MPCQ_LANE_REF_PARAM)
                 for (int j = 0; j < MC; j++) {
                     T zt = 0;
 #pragma unroll
-                    for (int k = 0; k < NC; k++) zt = tfma(WtA[j * NC + k], xi[k], zt);
+                    for (int k = 0; k < NC; k++) zt = tt_fma(WtA[j * NC + k], xi[k], zt);
                     T rj = rho, rij = rinv;
                     if (!ALL_INEQ) {
                         rj = ctype[j] == -1 ? T(kRhoMin) : rho * base[L.rscale + j];
                         rij = T(1) / rj;
                     }
-                    const T v = tfma(alpha, zt, oma * z[j]);
-                    T zn = tfma(rij, y[j], v);
-                    if (!LFREE) zn = tmax(zn, lh[j * 64]);
-                    zn = tmin(zn, uh[j * 64]);
-                    y[j] = tfma(rj, v - zn, y[j]);
+                    const T v = tt_fma(alpha, zt, oma * z[j]);
+                    T zn = tt_fma(rij, y[j], v);
+                    if (!LFREE) zn = tt_max(zn, lh[j * 64]);
+                    zn = tt_min(zn, uh[j * 64]);
+                    y[j] = tt_fma(rj, v - zn, y[j]);
                     z[j] = zn;
                 }
             }
@@ -354,37 +347,37 @@ void MPCQ_LANE_KERNEL(AdmmArgs<T> a MPCQ_LANE_REF_PARAM)
             for (int j = 0; j < MC; j++) {
                 T s = 0;
 #pragma unroll
-                for (int k = 0; k < NC; k++) s = tfma(base[L.WtA + j * NC + k], xs[k], s);
+                for (int k = 0; k < NC; k++) s = tt_fma(base[L.WtA + j * NC + k], xs[k], s);
                 const T r = s - z[j];
                 const T ei = base[L.Einv + j];
-                ax_z = tmax(ax_z, tabs(r));
-                ax_zs = tmax(ax_zs, tabs(ei * r));
-                zn_r = tmax(zn_r, tabs(z[j]));
-                zn_s = tmax(zn_s, tabs(ei * z[j]));
-                axn_r = tmax(axn_r, tabs(s));
-                axn_s = tmax(axn_s, tabs(ei * s));
+                ax_z = tt_max(ax_z, tt_abs(r));
+                ax_zs = tt_max(ax_zs, tt_abs(ei * r));
+                zn_r = tt_max(zn_r, tt_abs(z[j]));
+                zn_s = tt_max(zn_s, tt_abs(ei * z[j]));
+                axn_r = tt_max(axn_r, tt_abs(s));
+                axn_s = tt_max(axn_s, tt_abs(ei * s));
             }
             T dr_r = 0, dr_s = 0, qn_r = 0, qn_s = 0, atyn_r = 0, atyn_s = 0, pxn_r = 0, pxn_s = 0;
 #pragma unroll
             for (int k = 0; k < NC; k++) {
                 T px = 0, aty = 0;
 #pragma unroll
-                for (int i = 0; i < NC; i++) px = tfma(base[L.PW + k * NC + i], xs[i], px);
+                for (int i = 0; i < NC; i++) px = tt_fma(base[L.PW + k * NC + i], xs[i], px);
 #pragma unroll
-                for (int j = 0; j < MC; j++) aty = tfma(base[L.Ah + j * NC + k], y[j], aty);
+                for (int j = 0; j < MC; j++) aty = tt_fma(base[L.Ah + j * NC + k], y[j], aty);
                 double qk = 0.0;
                 if (k < n) qk = a.mpc ? a.q_out[(size_t)b * n + k] : a.q[(size_t)b * n + k];
                 const T qh = (T)((qk * (double)base[L.D + k]) * c64);
                 const T r = (qh + px) + aty;
                 const T di = base[L.Dinv + k];
-                dr_r = tmax(dr_r, tabs(r));
-                dr_s = tmax(dr_s, tabs(di * r));
-                qn_r = tmax(qn_r, tabs(qh));
-                qn_s = tmax(qn_s, tabs(di * qh));
-                atyn_r = tmax(atyn_r, tabs(aty));
-                atyn_s = tmax(atyn_s, tabs(di * aty));
-                pxn_r = tmax(pxn_r, tabs(px));
-                pxn_s = tmax(pxn_s, tabs(di * px));
+                dr_r = tt_max(dr_r, tt_abs(r));
+                dr_s = tt_max(dr_s, tt_abs(di * r));
+                qn_r = tt_max(qn_r, tt_abs(qh));
+                qn_s = tt_max(qn_s, tt_abs(di * qh));
+                atyn_r = tt_max(atyn_r, tt_abs(aty));
+                atyn_s = tt_max(atyn_s, tt_abs(di * aty));
+                pxn_r = tt_max(pxn_r, tt_abs(px));
+                pxn_s = tt_max(pxn_s, tt_abs(di * px));
             }
             const T cinv = base[L.cs + 1];
             const T pri_res = scaled_term ? ax_z : ax_zs;
@@ -397,7 +390,7 @@ void MPCQ_LANE_KERNEL(AdmmArgs<T> a MPCQ_LANE_REF_PARAM)
                 const T ea = eps_abs * mul, er = eps_rel * mul;
                 bool prim_ok = (m == 0), dual_ok = false, prim_inf = false, dual_inf = false;
                 if (m > 0) {
-                    const T ep = ea + er * (scaled_term ? tmax(zn_r, axn_r) : tmax(zn_s, axn_s));
+                    const T ep = ea + er * (scaled_term ? tt_max(zn_r, axn_r) : tt_max(zn_s, axn_s));
                     if (pri_res < ep) {
                         prim_ok = true;
                     } else {
@@ -407,8 +400,8 @@ void MPCQ_LANE_KERNEL(AdmmArgs<T> a MPCQ_LANE_REF_PARAM)
                                                                 (T)st.eps_prim_inf * mul, scaled_term);
                     }
                 }
-                const T ed = ea + er * (scaled_term ? tmax(tmax(qn_r, atyn_r), pxn_r)
-                                                    : cinv * tmax(tmax(qn_s, atyn_s), pxn_s));
+                const T ed = ea + er * (scaled_term ? tt_max(tt_max(qn_r, atyn_r), pxn_r)
+                                                    : cinv * tt_max(tt_max(qn_s, atyn_s), pxn_s));
                 if (dua_res < ed) {
                     dual_ok = true;
                 } else {
@@ -426,13 +419,13 @@ void MPCQ_LANE_KERNEL(AdmmArgs<T> a MPCQ_LANE_REF_PARAM)
             bool term = false;
             if (at_check) term = check_termination(0);
             if (!term && at_adapt) {  // adapt_rho / compute_rho_estimate (scaled-space norms)
-                const T pr = ax_z / (tmax(zn_r, axn_r) + T(kDivisionTol));
-                const T dn = tmax(tmax(qn_r, atyn_r), pxn_r);
+                const T pr = ax_z / (tt_max(zn_r, axn_r) + T(kDivisionTol));
+                const T dn = tt_max(tt_max(qn_r, atyn_r), pxn_r);
                 const T du = dr_r / (dn + T(kDivisionTol));
                 T rn = rho * (T)sqrt((double)(pr / (du + T(kDivisionTol))));
-                rn = tmin(tmax(rn, T(kRhoMin)), T(kRhoMax));
+                rn = tt_min(tt_max(rn, T(kRhoMin)), T(kRhoMax));
                 if (rn > rho * (T)st.adaptive_rho_tolerance || rn < rho / (T)st.adaptive_rho_tolerance) {
-                    rho = tmin(tmax(rn, T(kRhoMin)), T(kRhoMax));
+                    rho = tt_min(tt_max(rn, T(kRhoMin)), T(kRhoMax));
                     rinv = T(1) / rho;
 #pragma unroll 1
                     for (int k = 0; k < NC; k++) dk[k * 64] = T(1) / (T(1) + rho * op.lam[k]);
@@ -457,7 +450,7 @@ void MPCQ_LANE_KERNEL(AdmmArgs<T> a MPCQ_LANE_REF_PARAM)
         if (has_sol) {
             T s = 0;
 #pragma unroll
-            for (int k = 0; k < NC; k++) s = tfma(op.W[i * NC + k], xs[k], s);
+            for (int k = 0; k < NC; k++) s = tt_fma(op.W[i * NC + k], xs[k], s);
             v = (double)s * (double)op.D[i];
         } else {
             v = __builtin_nan("");
@@ -501,12 +494,12 @@ __global__ __launch_bounds__(64) void warm_start_kernel(AdmmArgs<T> a, int nc, i
     auto xh = [&](int i) -> T { return i < n ? (T)(x[(size_t)b * n + i] * (double)op.Dinv[po + i]) : T(0); };
     for (int k = 0; k < nc; k++) {
         T s = 0;
-        for (int i = 0; i < nc; i++) s = tfma(op.Winv[po + (size_t)k * nc + i], xh(i), s);
+        for (int i = 0; i < nc; i++) s = tt_fma(op.Winv[po + (size_t)k * nc + i], xh(i), s);
         a.xs[(size_t)b * nc + k] = s;
     }
     for (int j = 0; j < mc; j++) {
         T s = 0;
-        for (int k = 0; k < nc; k++) s = tfma(op.Ah[po + (size_t)j * nc + k], xh(k), s);
+        for (int k = 0; k < nc; k++) s = tt_fma(op.Ah[po + (size_t)j * nc + k], xh(k), s);
         a.zs[(size_t)b * mc + j] = s;
         a.ys[(size_t)b * mc + j] =
             j < m ? (T)((y[(size_t)b * m + j] * (double)op.Einv[po + j]) * (double)op.cs[po]) : T(0);

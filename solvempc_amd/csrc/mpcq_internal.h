@@ -658,6 +658,26 @@ inline bool smallest_cap(const Cap (&caps)[K], int n, int m, int *nc, int *mc)
         }
     return best >= 0;
 }
+
+// Launch of a post-pass with one workgroup per QP and `lds` bytes of dynamic LDS (polish, the sensitivities): as
+// many workgroups as the LDS lets a CU hold (at most 8) on each of `cus` CUs, striding over the batch.
+// static_lds: the kernel's static LDS, counted with the dynamic part against the CU's 160 KiB.  0 launched,
+// -1 the LDS does not fit, -2 HIP error (*err).
+template <typename Args>
+inline int launch_per_qp(void (*kernel)(Args), const Args &a, int batch, int threads, size_t lds, size_t static_lds,
+                         int cus, hipStream_t s, hipError_t *err)
+{
+    constexpr size_t kCuLds = 160 * 1024;
+    if (lds + static_lds > kCuLds) return -1;
+    if (lds > 64 * 1024 &&
+        (*err = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
+        return -2;
+    const size_t fit = kCuLds / (lds + static_lds);
+    const int per_cu = fit > 8 ? 8 : (int)fit, all = (cus > 1 ? cus : 1) * per_cu;  // (fit >= 1: checked above)
+    hipLaunchKernelGGL(kernel, dim3(batch < all ? batch : all), dim3(threads), lds, s, a);
+    *err = hipGetLastError();
+    return *err == hipSuccess ? 0 : -2;
+}
 }  // namespace mpcq
 
 // Launchers that are not typed on T (extern "C" so the host library links them without templates).

@@ -30,50 +30,10 @@
 #include <cstdlib>
 
 #include "mpcq_internal.h"
+#include "mpcq_lane.h"
 #include "mpcq_wave.h"
 
 namespace mpcq {
-
-__device__ inline double mimo_limit_scaling(double d)
-{
-    d = d < kMinScaling ? 1.0 : d;
-    return d > kMaxScaling ? kMaxScaling : d;
-}
-
-// inclusive max scans over lanes 0..31 of non-negative values (DPP row shifts read 0 outside the row,
-// then one cross-row readlane); lanes >= 32 are ignored by the callers
-template <int CTRL> __device__ __forceinline__ double dpp_zero(double v)
-{  // (bound_ctrl: a lane without a source reads 0, with no zeroed destination to copy first)
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u, CTRL, 0xF, 0xF, true);
-    const unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, true);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ double readlane_f64(double v, int l)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ double lane_prefix_max(double v, int lane)
-{
-    v = fmax(v, dpp_zero<0x111>(v));
-    v = fmax(v, dpp_zero<0x112>(v));
-    v = fmax(v, dpp_zero<0x114>(v));
-    v = fmax(v, dpp_zero<0x118>(v));
-    const double s = readlane_f64(v, 15);
-    return (lane >= 16) ? fmax(v, s) : v;
-}
-__device__ __forceinline__ double lane_suffix_max(double v, int lane)
-{
-    v = fmax(v, dpp_zero<0x101>(v));
-    v = fmax(v, dpp_zero<0x102>(v));
-    v = fmax(v, dpp_zero<0x104>(v));
-    v = fmax(v, dpp_zero<0x108>(v));
-    const double s = readlane_f64(v, 16);
-    return (lane < 16) ? fmax(v, s) : v;
-}
 
 // ----------------------------------------------------------------------------------------------
 // setup: one 1024-thread workgroup (16 waves) per plant, two plants per CU; LDS carve (doubles), under
@@ -447,8 +407,10 @@ __global__ __launch_bounds__(kMimoSetupThreads, 8) void mimo_setup_kernel(MimoSe
                     w0 = fmax(w0, Ec[k * nu + q] * fabs(K0[q * nu + c]));
                     w1 = fmax(w1, fabs(K0[c * nu + q]) * Dc[k * nu + q]);
                 }
-            w0 = lane_suffix_max(w0, k);
-            w1 = lane_prefix_max(w1, k);
+            // (inclusive max scans over lanes 0..31 of non-negative values; the whole wave is here)
+            const auto maxd = [](double a, double b) { return fmax(a, b); };
+            w0 = lane_suffix(w0, maxd, k);
+            w1 = lane_prefix(w1, maxd, k);
             if (k < 32) {
                 wk[k * 4 + c] = w0;
                 wk[128 + k * 4 + c] = w1;
@@ -461,8 +423,8 @@ __global__ __launch_bounds__(kMimoSetupThreads, 8) void mimo_setup_kernel(MimoSe
         __syncthreads();
         if (pass > 0) {
             const double mean = (red[0] + red[1]) / n;
-            const double qn = mimo_limit_scaling(0.0);  // |q^| = 0 at setup
-            cst *= 1.0 / mimo_limit_scaling(fmax(mean, qn));
+            const double qn = limit_scaling(0.0);  // |q^| = 0 at setup
+            cst *= 1.0 / limit_scaling(fmax(mean, qn));
         }
         if (pass == a.scaling) break;
         if (pass == 1) MPCQ_SSTAMP(10);
@@ -470,8 +432,8 @@ __global__ __launch_bounds__(kMimoSetupThreads, 8) void mimo_setup_kernel(MimoSe
             const int bj = t / nu, c = t % nu;
             const double va = wk[bj * 4 + c], vr = wk[128 + bj * 4 + c];  // suffix / prefix maxima (wave 0)
             const double v = fmax(cst * Dc[t] * cmt, va * Dc[t]);
-            Dn[t] = Dc[t] / sqrt(mimo_limit_scaling(v));
-            En[t] = Ec[t] / sqrt(mimo_limit_scaling(Ec[t] * vr));
+            Dn[t] = Dc[t] / sqrt(limit_scaling(v));
+            En[t] = Ec[t] / sqrt(limit_scaling(Ec[t] * vr));
         }
         __syncthreads();
         if (pass == 1) MPCQ_SSTAMP(11);
@@ -565,42 +527,15 @@ __device__ __forceinline__ void stb(double *arr, int lane, const B4 &x)
     p[0] = make_double2(x.v[0], x.v[1]);
     p[1] = make_double2(x.v[2], x.v[3]);
 }
-// DPP move whose lanes without a source read 0 (row shifts)
-template <int CTRL> __device__ __forceinline__ double dpp0(double v)
-{  // (bound_ctrl: a lane without a source reads 0, with no zeroed destination to copy first)
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u, CTRL, 0xF, 0xF, true);
-    const unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, true);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ double readlane_d(double v, int l)
+// inclusive sums over lanes 0..31 (horizon blocks; N <= 32; lanes >= 32 are ignored by the callers; for the
+// suffix, lanes N..31 must hold 0)
+__device__ __forceinline__ double lane_psum(double v, int lane)
 {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    return lane_prefix(v, [](double a, double b) { return a + b; }, lane);
 }
-// inclusive prefix over lanes 0..31 (horizon blocks; N <= 32): row_shr 1, 2, 4, 8, then row 1 adds
-// lane 15's total
-__device__ __forceinline__ double lane_prefix(double v, int lane)
+__device__ __forceinline__ double lane_ssum(double v, int lane)
 {
-    v += dpp0<0x111>(v);
-    v += dpp0<0x112>(v);
-    v += dpp0<0x114>(v);
-    v += dpp0<0x118>(v);
-    const double s = readlane_d(v, 15);
-    return (lane >= 16) ? v + s : v;
-}
-// inclusive suffix over lanes 0..31 (lanes N..31 must hold 0): row_shl 1, 2, 4, 8, then row 0 adds
-// lane 16's total
-__device__ __forceinline__ double lane_suffix(double v, int lane)
-{
-    v += dpp0<0x101>(v);
-    v += dpp0<0x102>(v);
-    v += dpp0<0x104>(v);
-    v += dpp0<0x108>(v);
-    const double s = readlane_d(v, 16);
-    return (lane < 16) ? v + s : v;
+    return lane_suffix(v, [](double a, double b) { return a + b; }, lane);
 }
 
 #define MPCQ_MSTAMP(k, v)                                                                  \
@@ -756,7 +691,7 @@ __global__ __launch_bounds__(kMimoThreads, MPCQ_MIMO_WAVES_PER_EU) void mimo_sol
     auto scan_x = [&](double v, bool suffix) -> const double * {
         double *buf = s_xb[xb];
         xb = (xb + 1) & 3;
-        const double p = suffix ? lane_suffix(v, lane) : lane_prefix(v, lane);
+        const double p = suffix ? lane_ssum(v, lane) : lane_psum(v, lane);
         if (k < 32) buf[vi] = p;
         return buf;
     };
@@ -777,7 +712,7 @@ __global__ __launch_bounds__(kMimoThreads, MPCQ_MIMO_WAVES_PER_EU) void mimo_sol
     const double k0cc = s_K0[(c & 3) * 5];
     auto A_of = [&](double xv) {
         if constexpr (DK) {
-            const double p = lane_prefix(valid ? vD * xv : 0.0, lane);
+            const double p = lane_psum(valid ? vD * xv : 0.0, lane);
             return valid ? vE * (k0cc * p) : 0.0;
         } else {
             const double *bf = scan_x(valid ? vD * xv : 0.0, false);
@@ -788,7 +723,7 @@ __global__ __launch_bounds__(kMimoThreads, MPCQ_MIMO_WAVES_PER_EU) void mimo_sol
     // A^' [w_top; w_bot] = D (L (x) K0)' E d, d = w_top - w_bot
     auto At_of = [&](double d) {
         if constexpr (DK) {
-            const double p = lane_suffix(valid ? vE * d : 0.0, lane);
+            const double p = lane_ssum(valid ? vE * d : 0.0, lane);
             return valid ? vD * (k0cc * p) : 0.0;
         } else {
             const double *bf = scan_x(valid ? vE * d : 0.0, true);
@@ -799,7 +734,7 @@ __global__ __launch_bounds__(kMimoThreads, MPCQ_MIMO_WAVES_PER_EU) void mimo_sol
     auto At_of2 = [&](double d1, double d2, double &o1, double &o2) {
         const double E = valid ? vE : 0.0;
         if constexpr (DK) {
-            const double p1 = lane_suffix(E * d1, lane), p2 = lane_suffix(E * d2, lane);
+            const double p1 = lane_ssum(E * d1, lane), p2 = lane_ssum(E * d2, lane);
             o1 = valid ? vD * (k0cc * p1) : 0.0;
             o2 = valid ? vD * (k0cc * p2) : 0.0;
         } else {

@@ -23,8 +23,6 @@
 // The chain rule of the step gains (q = Fx X + Fu U + Frs yref, u = W0 + Sbar X + Ku U) is the kernel's tail: gq
 // and gu of a right-hand side are still in LDS, one thread per output element, sums in ascending row index.
 // No atomics anywhere: two calls give identical bits.  Nothing of the context is written.
-#include <algorithm>
-
 #include "mpcq_internal.h"
 
 namespace mpcq {
@@ -464,26 +462,13 @@ extern "C" int mpcq_internal_mimo_sens_launch(const mpcq::MimoSensArgs *a, int c
     if (a->nx <= 0 || a->nx > 12 || a->ny <= 0 || a->ny > 12 || a->N <= 0 || a->N > 32 || n > 128) return -1;
     if (a->n_rhs < 1 || a->n_rhs > 4) return -1;
     if (a->batch <= 0) return 0;
-    const size_t lds = mpcq_internal_mimo_sens_lds(n);
-    if (lds + 256 > 160 * 1024) return -1;  // (+ the kernel's few static words)
-    const void *fn = nullptr;
+    void (*kernel)(mpcq::MimoSensArgs) = nullptr;
     switch (a->nu) {
-    case 1: fn = (const void *)mpcq::mimo_sens_kernel<1>; break;
-    case 2: fn = (const void *)mpcq::mimo_sens_kernel<2>; break;
-    case 4: fn = (const void *)mpcq::mimo_sens_kernel<4>; break;
+    case 1: kernel = mpcq::mimo_sens_kernel<1>; break;
+    case 2: kernel = mpcq::mimo_sens_kernel<2>; break;
+    case 4: kernel = mpcq::mimo_sens_kernel<4>; break;
     default: return -1;
     }
-    if (lds > 64 * 1024 &&
-        (*err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
-        return -2;
-    // as many workgroups as the LDS and the wave slots let a CU hold (at most 8), striding over the batch
-    const int per_cu = (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (lds + 256)));
-    const dim3 grid(std::min(a->batch, std::max(1, cus) * per_cu)), block(mpcq::kMsThreads);
-    switch (a->nu) {
-    case 1: hipLaunchKernelGGL(mpcq::mimo_sens_kernel<1>, grid, block, lds, s, *a); break;
-    case 2: hipLaunchKernelGGL(mpcq::mimo_sens_kernel<2>, grid, block, lds, s, *a); break;
-    default: hipLaunchKernelGGL(mpcq::mimo_sens_kernel<4>, grid, block, lds, s, *a); break;
-    }
-    *err = hipGetLastError();
-    return *err == hipSuccess ? 0 : -2;
+    // (256: the kernel's few static words)
+    return mpcq::launch_per_qp(kernel, *a, a->batch, mpcq::kMsThreads, mpcq_internal_mimo_sens_lds(n), 256, cus, s, err);
 }

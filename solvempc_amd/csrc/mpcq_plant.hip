@@ -20,35 +20,11 @@
 //      place; U += x0 when solved (:105).
 // The two halves share the iteration counter (checks and adapt_rho fall on the same iterations);
 // a finished half idles until its partner finishes.
+#include "mpcq_lane.h"
 #include "mpcq_wave.h"
 
 namespace mpcq {
 
-
-// 32-lane (half-wave) reductions with every lane of the half ending on the same bits: DPP within the
-// 16-lane rows, then v_permlane16_swap (rows 0 <-> 1 and 2 <-> 3: never across the halves).
-template <typename F> __device__ __forceinline__ float swap16(float v, F op)
-{
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return op(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-template <typename F> __device__ __forceinline__ double swap16(double v, F op)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)u, hi = (unsigned)(u >> 32);
-    auto r = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    auto mk = [](unsigned l, unsigned hh) { return __longlong_as_double((long long)(((unsigned long long)hh << 32) | l)); };
-    return op(mk(r[0], h[0]), mk(r[1], h[1]));
-}
-template <typename T, typename F> __device__ __forceinline__ T half_reduce(T v, F op)
-{
-    v = op(v, dpp_t<0xB1>(v));   // quad_perm [1,0,3,2]
-    v = op(v, dpp_t<0x4E>(v));   // quad_perm [2,3,0,1]
-    v = op(v, dpp_t<0x141>(v));  // row_half_mirror
-    v = op(v, dpp_t<0x140>(v));  // row_mirror
-    return swap16(v, op);
-}
 // max / max of magnitudes as single v_max instructions (|.| as a source modifier).  LLVM's maxnum adds a
 // canonicalising v_max x, x per operand here; on the finite, non-NaN values these norms and scalings see
 // the results are the same (max is exact).
@@ -90,58 +66,18 @@ __device__ __forceinline__ bool hany(bool p)  // any lane of this lane's half
     return ((threadIdx.x & 32) ? (b >> 32) : (b & 0xffffffffull)) != 0ull;
 }
 
-__device__ inline double limit_scaling_p(double d)
-{
-    d = d < kMinScaling ? 1.0 : d;
-    return d > kMaxScaling ? kMaxScaling : d;
-}
-
-// DPP move whose lanes without a source (row shifts) or outside the row mask RM read 0.  With every row
-// enabled the zero comes from bound_ctrl (no old value: no zeroing move before each DPP move).
-template <int CTRL, int RM> __device__ __forceinline__ unsigned dpp0_u(unsigned v)
-{
-    if constexpr (RM == 0xF) return (unsigned)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
-    else return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, RM, 0xF, false);
-}
-template <int CTRL, int RM = 0xF> __device__ __forceinline__ float dpp0(float v)
-{
-    return __uint_as_float(dpp0_u<CTRL, RM>(__float_as_uint(v)));
-}
-template <int CTRL, int RM = 0xF> __device__ __forceinline__ double dpp0(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = dpp0_u<CTRL, RM>((unsigned)u), hi = dpp0_u<CTRL, RM>((unsigned)(u >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ float readlane_t(float v, int l)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ double readlane_t(double v, int l)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 // Inclusive scans over the 32 lanes of each half (lane r = horizon step r), op with identity 0 (sums,
-// maxima of non-negative values).  Prefix: row_shr 1, 2, 4, 8 inside the 16-lane rows, then
-// row_bcast:15 into rows 1 and 3.  Suffix: row_shl 1, 2, 4, 8, then rows 0 and 2 take lane 16's /
-// lane 48's total.  Call with the whole wave active (DPP and readlane read other lanes).
+// maxima of non-negative values): mpcq_lane.h's row scans, then the carry of both halves at once.  Prefix:
+// row_bcast:15 into rows 1 and 3.  Suffix: rows 0 and 2 take lane 16's / lane 48's total.  Call with the
+// whole wave active (DPP and readlane read other lanes).
 template <typename T, typename F> __device__ __forceinline__ T half_prefix(T v, F op)
 {
-    v = op(v, dpp0<0x111>(v));
-    v = op(v, dpp0<0x112>(v));
-    v = op(v, dpp0<0x114>(v));
-    v = op(v, dpp0<0x118>(v));
-    return op(v, dpp0<0x142, 0xA>(v));
+    v = row_prefix(v, op);
+    return op(v, dpp_t<0x142, 0xA>(v));
 }
 template <typename T, typename F> __device__ __forceinline__ T half_suffix(T v, F op, int lane)
 {
-    v = op(v, dpp0<0x101>(v));
-    v = op(v, dpp0<0x102>(v));
-    v = op(v, dpp0<0x104>(v));
-    v = op(v, dpp0<0x108>(v));
+    v = row_suffix(v, op);
     const T s0 = readlane_t(v, 16), s1 = readlane_t(v, 48);
     return (lane & 16) ? v : op(v, (lane & 32) ? s1 : s0);
 }
@@ -683,8 +619,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 20 ? W
     for (int it = 0; it < st.scaling; it++) {
         const double emax = l_suffix_max<LAY>(Er, lane), dpre = l_prefix_max<LAY>(Dr, lane);
         const double va = (aK0 * Dr) * emax, ve = (aK0 * Er) * dpre;
-        const double dt = 1.0 / sqrt(limit_scaling_p(fmax(cp * vp, va)));
-        const double et = 1.0 / sqrt(limit_scaling_p(ve));
+        const double dt = 1.0 / sqrt(limit_scaling(fmax(cp * vp, va)));
+        const double et = 1.0 / sqrt(limit_scaling(ve));
         if (r < NC) S.tmp()[r] = lr ? dt : 0.0;
         wave_sync();
         double cn = 0.0;
@@ -703,7 +639,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC <= 20 ? W
         double cb[1] = {lr ? cn : 0.0};
         lay_reduce_k<LAY, NC, 1, 1u>(S.red(), cb, r, lane);
         const double mean = cb[0] / n;
-        cp = 1.0 / limit_scaling_p(fmax(mean, 1.0));
+        cp = 1.0 / limit_scaling(fmax(mean, 1.0));
         cost *= cp;
     }
     if (st.scaling > 0) {

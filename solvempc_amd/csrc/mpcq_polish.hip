@@ -5,12 +5,11 @@
 //   1. scaled data P^ = c D P D (symmetrised from P's upper triangle), A^ = E A D, q^ = c D q, l^ = E l,
 //      u^ = E u from the context's unscaled setup data and the plant's Ruiz scaling;
 //   2. the final scaled iterate x^ = W x', z^, y^ from the warm state (type T, converted);
-//   3. OSQP's active sets: row lower-active when z^ - l^ < -y^, upper-active when u^ - z^ < y^; A_red holds
-//      the lower-active rows followed by the upper-active ones (mr rows, 0 <= mr <= m);
-//   4. the regularised KKT system [P^ + delta I, A_red'; A_red, -delta I] s = [-q^; l^_low; u^_upp] by
-//      Cholesky of H = P^ + delta I and of the Schur complement S = delta I + A_red H^-1 A_red' (positive
-//      definite thanks to delta, whatever the rank of A_red), then polish_refine_iter steps of iterative
-//      refinement against the unregularised matrix, s += K_reg^-1 (b - K s);
+//   3. OSQP's active sets and A_red, the lower-active rows followed by the upper-active ones (mr rows,
+//      0 <= mr <= m): WaveKkt::active_sets (mpcq_wavekkt.h);
+//   4. the regularised KKT system [P^ + delta I, A_red'; A_red, -delta I] s = [-q^; l^_low; u^_upp] and
+//      polish_refine_iter steps of iterative refinement against the unregularised matrix:
+//      WaveKkt::schur_from_rows and solve_refined;
 //   5. x_pol = s[0:n], z_pol = A^ x_pol, y_pol scattered from s[n:], then project_normalcone:
 //      t = z + y, z = clip(t, l^, u^), y = t - z;
 //   6. success when both residuals (termination norms) are reduced, or one is and the other was already
@@ -18,15 +17,11 @@
 //      written, else the ADMM result stays;
 //   7. in an MPC step, U += x[0] for every SOLVED QP, polished or not.
 //
-// Layout: matrices in LDS at odd fp64 strides (lane i walks row i: conflict-free; a broadcast row costs
-// one access), vectors in registers, lane i holding element i (n <= 32 and m <= 64 both fit the 64 lanes).
-// A triangular solve keeps its vector in registers: step k broadcasts element k with a shuffle and every
-// later lane subtracts its multiple, so it needs no LDS write and no barrier.  A shared plant's P^, A^ and
-// the factor of H are formed once per workgroup; the grid strides over the batch.
-#include <algorithm>
-
+// Layout: mpcq_wavekkt.h's (matrices in LDS at odd fp64 strides, vectors in registers, lane i holding element i);
+// the forming of step 1's P^ and A^ and the factor of H is WaveKkt::form.  A shared plant's P^, A^ and the factor
+// of H are formed once per workgroup; the grid strides over the batch.
 #include "mpcq_internal.h"
-#include "mpcq_wavechol.h"
+#include "mpcq_wavekkt.h"
 
 namespace mpcq {
 
@@ -35,19 +30,15 @@ __global__ __launch_bounds__(64) void polish_kernel(PolishArgs a)
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
     const int n = a.n, m = a.m, nc = a.nc, mc = a.mc;
-    const int ldn = n | 1, ldS = m | 1;
     const bool ln = lane < n, lm = lane < m;
-    double *const Ph = lds;                 // n x ldn   P^
-    double *const Ah = Ph + n * ldn;        // m x ldn   A^
-    double *const Lh = Ah + m * ldn;        // n x ldn   Cholesky factor of H = P^ + delta I
-    double *const V = Lh + n * ldn;         // m x ldn   row j: L^-1 a_red_j
-    double *const S = V + m * ldn;          // m x ldS   Schur complement, then its factor
-    double *const xv = S + m * ldS;         // n         staging (an n-vector read by every lane)
-    double *const mv = xv + n;              // m         staging (an m-vector)
-    double *const dH = mv + m;              // n         1 / diag of Lh
-    double *const dS = dH + n;              // m         1 / diag of the factor of S
-    double *const bact = dS + m;            // m         rhs of the reduced rows (l^ / u^ of the active rows)
-    int *const act = (int *)(bact + m);     // m         row of A^ behind each reduced row
+    WaveKkt K(n, m, a.delta, lane);
+    const int ldn = K.ldn;
+    double *const V = K.head(lds);          // m x ldn   row j: L^-1 a_red_j
+    K.S = V + m * ldn;                      // m x ldS   Schur complement, then its factor
+    K.ldS = m | 1;
+    double *const bact = K.tail(K.S + m * K.ldS);  // m  rhs of the reduced rows (l^ / u^ of the active rows)
+    K.act = (int *)(bact + m);
+    double *const Ph = K.Ph, *const Ah = K.Ah, *const xv = K.xv, *const mv = K.mv;
     const OpsLayout L = OpsLayout::make(nc, mc);
     const double nanv = __builtin_nan("");
     bool have_plant = false, h_ok = false;
@@ -71,20 +62,7 @@ __global__ __launch_bounds__(64) void polish_kernel(PolishArgs a)
 
         // ---- 1. scaled data (once per workgroup for a shared plant) and the factor of H
         if (!a.shared || !have_plant) {
-            const double *P = a.P + pp * n * n, *A = a.A + pp * m * n;
-            for (int e = lane; e < n * n; e += 64) {
-                const int i = e / n, j = e - i * n;
-                const double p = i <= j ? P[i * n + j] : P[j * n + i];  // upper triangle, as OSQP reads it
-                const double v = (c * ops[L.D + i]) * p * ops[L.D + j];
-                Ph[i * ldn + j] = v;
-                Lh[i * ldn + j] = i == j ? v + a.delta : v;
-            }
-            for (int e = lane; e < m * n; e += 64) {
-                const int j = e / n, k = e - j * n;
-                Ah[j * ldn + k] = (ops[L.E + j] * A[j * n + k]) * ops[L.D + k];
-            }
-            __syncthreads();
-            h_ok = wave_cholesky(Lh, ldn, n, dH, lane);
+            h_ok = K.form(a.P + pp * n * n, a.A + pp * m * n, ops + L.D, ops + L.E, c);
             have_plant = true;
         }
 
@@ -94,12 +72,9 @@ __global__ __launch_bounds__(64) void polish_kernel(PolishArgs a)
         const double up = lm ? a.u[(size_t)b * m + lane] * Ej : 0.0;
 
         // ---- 2. final scaled iterate
-        auto state = [&](const void *p, size_t i) -> double {
-            return a.is_f32 ? (double)((const float *)p)[i] : ((const double *)p)[i];
-        };
-        if (ln) xv[lane] = state(a.xs, (size_t)b * nc + lane);
-        const double zh = lm ? state(a.zs, (size_t)b * mc + lane) : 0.0;
-        const double yh = lm ? state(a.ys, (size_t)b * mc + lane) : 0.0;
+        if (ln) xv[lane] = warm_state(a.xs, a.is_f32, (size_t)b * nc + lane);
+        const double zh = lm ? warm_state(a.zs, a.is_f32, (size_t)b * mc + lane) : 0.0;
+        const double yh = lm ? warm_state(a.ys, a.is_f32, (size_t)b * mc + lane) : 0.0;
         __syncthreads();
         double xh = 0.0;
         if (ln)
@@ -107,85 +82,14 @@ __global__ __launch_bounds__(64) void polish_kernel(PolishArgs a)
         __syncthreads();
 
         // ---- 3. active sets
-        const bool low = lm && (zh - lo < -yh);
-        const bool upp = lm && !low && (up - zh < yh);  // (exclusive by l <= u; enforced for the bounds' sake)
-        const unsigned long long mlow = __ballot(low), mupp = __ballot(upp);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        const int n_low = __popcll(mlow), mr = n_low + __popcll(mupp);
-        const int pos = low ? __popcll(mlow & below) : n_low + __popcll(mupp & below);
-        if (low || upp) {
-            act[pos] = lane;
-            bact[pos] = low ? lo : up;
-        }
-        __syncthreads();
-        const bool lr = lane < mr;
-        const int aj = lr ? act[lane] : 0;
-        const double b2 = lr ? bact[lane] : 0.0;
-        const double b1 = -qh;
+        K.active_sets(zh, yh, lo, up, bact);
+        const bool low = K.low, upp = K.upp, lr = K.lr;
+        const int mr = K.mr, pos = K.pos;
 
-        // ---- 4. Schur complement S = delta I + V V', V = (L^-1 A_red')' (lane j: row j, forward substitution)
-        bool ok = h_ok;
-        if (ok) {
-            if (lr) {
-                for (int i = 0; i < n; i++) {
-                    double v = Ah[aj * ldn + i];
-                    for (int k = 0; k < i; k++) v -= Lh[i * ldn + k] * V[lane * ldn + k];
-                    V[lane * ldn + i] = v * dH[i];
-                }
-            }
-            __syncthreads();
-            if (lr) {
-                for (int j = 0; j <= lane; j++) {
-                    double v = j == lane ? a.delta : 0.0;
-                    for (int k = 0; k < n; k++) v += V[lane * ldn + k] * V[j * ldn + k];
-                    S[lane * ldS + j] = v;
-                }
-            }
-            __syncthreads();
-            ok = wave_cholesky(S, ldS, mr, dS, lane);
-        }
-
-        // K_reg^-1 [r1; r2]: nu = S^-1 (A_red H^-1 r1 - r2), x = H^-1 (r1 - A_red' nu)
-        auto kkt_solve = [&](double r1, double r2, double &sx, double &sn) {
-            const double t = wave_chol_solve(Lh, ldn, n, dH, r1, lane);
-            if (ln) xv[lane] = t;
-            __syncthreads();
-            double w = 0.0;
-            if (lr) {
-                for (int k = 0; k < n; k++) w += Ah[aj * ldn + k] * xv[k];
-                w -= r2;
-            }
-            sn = wave_chol_solve(S, ldS, mr, dS, w, lane);
-            if (lr) mv[lane] = sn;
-            __syncthreads();
-            double r = r1;
-            if (ln)
-                for (int j = 0; j < mr; j++) r -= Ah[act[j] * ldn + lane] * mv[j];
-            sx = wave_chol_solve(Lh, ldn, n, dH, r, lane);
-            __syncthreads();  // (xv, mv free again)
-        };
-
+        // ---- 4. the reduced KKT system [-q^; l^_low; u^_upp], refined
+        const bool ok = h_ok && K.schur_from_rows(V, ldn);
         double sx = 0.0, sn = 0.0;
-        if (ok) {
-            kkt_solve(b1, b2, sx, sn);
-            for (int it = 0; it < a.refine; it++) {  // s += K_reg^-1 (b - K s), K without delta
-                if (ln) xv[lane] = sx;
-                if (lr) mv[lane] = sn;
-                __syncthreads();
-                double r1 = b1, r2 = b2;
-                if (ln) {
-                    for (int k = 0; k < n; k++) r1 -= Ph[lane * ldn + k] * xv[k];
-                    for (int j = 0; j < mr; j++) r1 -= Ah[act[j] * ldn + lane] * mv[j];
-                }
-                if (lr)
-                    for (int k = 0; k < n; k++) r2 -= Ah[aj * ldn + k] * xv[k];
-                __syncthreads();
-                double dx, dn;
-                kkt_solve(r1, r2, dx, dn);
-                sx += dx;
-                sn += dn;
-            }
-        }
+        if (ok) K.solve_refined(-qh, lr ? bact[lane] : 0.0, a.refine, sx, sn);
 
         // ---- 5./6. residuals of a point (x in xv, y in mv; lane j's (A^ x)_j and z_j): termination norms
         auto row_ax = [&]() {
@@ -286,16 +190,5 @@ extern "C" int mpcq_internal_polish_launch(const mpcq::PolishArgs *a, int cus, h
     *err = hipSuccess;
     if (a->n <= 0 || a->n > 32 || a->m < 0 || a->m > 64) return -1;
     if (a->batch <= 0) return 0;
-    const size_t lds = polish_lds(a->n, a->m);
-    if (lds > 160 * 1024) return -1;
-    if (lds > 64 * 1024 &&
-        (*err = hipFuncSetAttribute((const void *)mpcq::polish_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds)) != hipSuccess)
-        return -2;
-    // one wave per workgroup; as many workgroups as the LDS lets a CU hold (at most 8), striding over the batch
-    const int per_cu = (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / lds));
-    const int grid = std::min(a->batch, std::max(1, cus) * per_cu);
-    hipLaunchKernelGGL(mpcq::polish_kernel, dim3(grid), dim3(64), lds, s, *a);
-    *err = hipGetLastError();
-    return *err == hipSuccess ? 0 : -2;
+    return mpcq::launch_per_qp(mpcq::polish_kernel, *a, a->batch, 64, polish_lds(a->n, a->m), 0, cus, s, err);
 }

@@ -9,6 +9,7 @@
 //   4. operator block for the ADMM kernel (padded to the kernel capacity).
 // Setup runs once per plant; it is cold-path code written for clarity, not speed.
 #include "mpcq_internal.h"
+#include "mpcq_lane.h"
 
 namespace mpcq {
 
@@ -16,12 +17,6 @@ namespace mpcq {
 __host__ __device__ inline size_t setup_scratch_len_dev(int n, int m)
 {
     return 7 * (size_t)n * n + (size_t)m * n + 3 * (size_t)n + 2 * (size_t)m + 64;
-}
-
-__device__ inline double limit_scaling(double d)
-{
-    d = d < kMinScaling ? 1.0 : d;
-    return d > kMaxScaling ? kMaxScaling : d;
 }
 
 __global__ __launch_bounds__(64) void setup_kernel(SetupArgs a)

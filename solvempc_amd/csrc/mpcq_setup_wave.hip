@@ -16,6 +16,7 @@
 // setup_wave_keep_kernel / setup_inv_keep_kernel (mpcq_update_P_A_device, rescale = 0) are the same bodies with the
 // scaling read from the plant's operator block instead of recomputed: the factor stage alone on new matrices.
 #include "mpcq_internal.h"
+#include "mpcq_lane.h"
 
 #include <algorithm>
 
@@ -52,38 +53,11 @@ struct SetupWaveShape {
     }
 };
 
-__device__ inline double limit_scaling_w(double d)
-{
-    d = d < kMinScaling ? 1.0 : d;
-    return d > kMaxScaling ? kMaxScaling : d;
-}
-
 // Whole-wave sum with every lane ending on the same bits (symmetric pairwise adds): DPP quad swaps and
 // row mirrors, then the 16/32-lane swaps (VALU only; a __shfl_xor ladder is 12 LDS-path permutes).
-template <int CTRL> __device__ inline double dpp_f64(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)u, (int)(unsigned)u, CTRL, 0xF, 0xF, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(u >> 32), (int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, false);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ inline double swap_sum_f64(double v, bool w32)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)u, hi = (unsigned)(u >> 32);
-    auto r = w32 ? __builtin_amdgcn_permlane32_swap(lo, lo, false, false) : __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto h = w32 ? __builtin_amdgcn_permlane32_swap(hi, hi, false, false) : __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    auto mk = [](unsigned l, unsigned hh) { return __longlong_as_double((long long)(((unsigned long long)hh << 32) | l)); };
-    return mk(r[0], h[0]) + mk(r[1], h[1]);
-}
 __device__ inline double wave_sum(double v)
 {
-    v = v + dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
-    v = v + dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
-    v = v + dpp_f64<0x141>(v);  // row_half_mirror
-    v = v + dpp_f64<0x140>(v);  // row_mirror
-    v = swap_sum_f64(v, false);
-    return swap_sum_f64(v, true);
+    return wave_reduce(v, [](double a, double b) { return a + b; });
 }
 
 // Pair u of round r of the circle ordering on ne (even) indices.
@@ -113,12 +87,12 @@ __device__ double ruiz_and_types(const SetupArgs &a, int pl, int t, int n, int m
             double vp = 0.0, va = 0.0;
             for (int i = 0; i < n; i++) vp = fmax(vp, fabs(Ph[i * ld + t]));
             for (int i = 0; i < m; i++) va = fmax(va, fabs(Ah[i * ld + t]));
-            Dt[t] = 1.0 / sqrt(limit_scaling_w(fmax(cp * vp, va)));
+            Dt[t] = 1.0 / sqrt(limit_scaling(fmax(cp * vp, va)));
         }
         for (int i = t; i < m; i += 64) {
             double v = 0.0;
             for (int j = 0; j < n; j++) v = fmax(v, fabs(Ah[i * ld + j]));
-            Et[i] = 1.0 / sqrt(limit_scaling_w(v));
+            Et[i] = 1.0 / sqrt(limit_scaling(v));
         }
         __syncthreads();
         for (int e = t; e < n * n; e += 64) {
@@ -143,8 +117,8 @@ __device__ double ruiz_and_types(const SetupArgs &a, int pl, int t, int n, int m
             for (int j = 0; j < n; j++) mean += Dt[j];
             mean /= n;
             for (int j = 0; j < n; j++) qn = fmax(qn, fabs(qh[j]));
-            qn = limit_scaling_w(qn);
-            const double ct = 1.0 / limit_scaling_w(fmax(mean, qn));
+            qn = limit_scaling(qn);
+            const double ct = 1.0 / limit_scaling(fmax(mean, qn));
             sh[1] = ct;
             sh[0] *= ct;
         }

@@ -22,6 +22,7 @@
 // columns for long.  A QP's arithmetic does not depend on which wave or phase runs it.
 #pragma once
 #include "mpcq_internal.h"
+#include "mpcq_lane.h"
 #include "mpcq_plant_sim.h"
 
 #include <cstdlib>
@@ -63,22 +64,6 @@ template <> struct Mf<double> {
     }
 };
 
-template <typename T> __device__ __forceinline__ T tt_fma(T a, T b, T c);
-template <> __device__ __forceinline__ float tt_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-template <> __device__ __forceinline__ double tt_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-template <typename T> __device__ __forceinline__ T tt_abs(T a) { return a < T(0) ? -a : a; }
-template <typename T> __device__ __forceinline__ T tt_max(T a, T b) { return a > b ? a : b; }
-template <typename T> __device__ __forceinline__ T tt_min(T a, T b) { return a < b ? a : b; }
-// IEEE minNum / maxNum / |x| at the operand's own width (__builtin_fmin & co. are the double builtins:
-// on float operands they widen, compare in fp64 and narrow back)
-__device__ __forceinline__ float tt_fmin(float a, float b) { return __builtin_fminf(a, b); }
-__device__ __forceinline__ double tt_fmin(double a, double b) { return __builtin_fmin(a, b); }
-__device__ __forceinline__ float tt_fmax(float a, float b) { return __builtin_fmaxf(a, b); }
-__device__ __forceinline__ double tt_fmax(double a, double b) { return __builtin_fmax(a, b); }
-__device__ __forceinline__ float tt_fabs(float a) { return __builtin_fabsf(a); }
-__device__ __forceinline__ double tt_fabs(double a) { return __builtin_fabs(a); }
-// max(m, |x|) for the infinity norms (one v_max with an |.| source modifier; equals OSQP's
-// c_max(m, c_absval(x)) for every non-NaN x).
 // min for the projection onto u without LLVM's NaN canonicalisation of the operands (a v_max x, x
 // per element per iteration): the hardware v_min returns the non-NaN operand, as fmin does.
 __device__ __forceinline__ float vmin(float a, float b)
@@ -93,41 +78,15 @@ __device__ __forceinline__ double vmin(double a, double b)
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// max(m, |x|) for the infinity norms (one v_max with an |.| source modifier; equals OSQP's
+// c_max(m, c_absval(x)) for every non-NaN x).
 template <typename T> __device__ __forceinline__ T nrm(T m, T x) { return tt_fmax(m, tt_fabs(x)); }
 
-// Reductions over the 4 lanes (groups) of one QP column (lanes c, c+16, c+32, c+48) with the gfx950
-// lane-swap instructions (v_permlane16_swap / v_permlane32_swap: VALU, no LDS round trip).  After a
-// swap of v with itself, {r[0], r[1]} = {own value, partner's value} in some order, so a symmetric
-// op of the pair gives the same, bit-identical result on all lanes of the column.
-template <typename F>
-__device__ __forceinline__ unsigned swap_combine(unsigned v, F op)
+// Reductions over the 4 lanes (groups) of one QP column (lanes c, c+16, c+32, c+48): the two lane swaps of
+// mpcq_lane.h's swap_op; a symmetric op gives the same, bit-identical result on all lanes of the column.
+template <typename T, typename F> __device__ __forceinline__ T col_reduce(T v, F op)
 {
-    auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    v = op(r[0], r[1]);
-    auto t = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return op(t[0], t[1]);
-}
-template <typename T, typename F> __device__ __forceinline__ T col_reduce(T v, F op);
-template <typename F> __device__ __forceinline__ float col_reduce(float v, F op)
-{
-    return __uint_as_float(swap_combine(__float_as_uint(v), [&](unsigned a, unsigned b) {
-        return __float_as_uint(op(__uint_as_float(a), __uint_as_float(b)));
-    }));
-}
-template <typename F> __device__ __forceinline__ double col_reduce(double v, F op)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    unsigned lo = (unsigned)u, hi = (unsigned)(u >> 32);
-    auto r = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    auto mk = [](unsigned l, unsigned hh) { return __longlong_as_double((long long)(((unsigned long long)hh << 32) | l)); };
-    double w = op(mk(r[0], h[0]), mk(r[1], h[1]));
-    const unsigned long long u2 = (unsigned long long)__double_as_longlong(w);
-    lo = (unsigned)u2;
-    hi = (unsigned)(u2 >> 32);
-    auto r2 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    auto h2 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return op(mk(r2[0], h2[0]), mk(r2[1], h2[1]));
+    return swap_op<32>(swap_op<16>(v, op), op);
 }
 template <typename T> __device__ __forceinline__ T col_max(T v)
 {
@@ -166,10 +125,8 @@ __device__ __forceinline__ double col_from(double v, int src, int g)
 }
 __device__ __forceinline__ int col_or(int v)
 {
-    return (int)swap_combine((unsigned)v, [](unsigned a, unsigned b) { return a | b; });
+    return (int)col_reduce((unsigned)v, [](unsigned a, unsigned b) { return a | b; });
 }
-__device__ __forceinline__ bool wave_any(bool p) { return __ballot(p) != 0ull; }
-__device__ __forceinline__ bool wave_all(bool p) { return __ballot(!p) == 0ull; }
 
 // Hide a pointer's provenance from LICM: the images are re-read from LDS in every phase of every
 // iteration instead of being hoisted into (and spilling) registers.

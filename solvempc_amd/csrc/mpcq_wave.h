@@ -14,6 +14,7 @@
 // launch to a wave launch at a phase boundary: both run OSQP's iteration on the same state (x', z, y,
 // rho), with the products summed in different orders (last-bit differences, like any two OSQP builds).
 #pragma once
+#include "mpcq_lane.h"
 #include "mpcq_plant_sim.h"
 #include "mpcq_tile.h"
 
@@ -26,33 +27,6 @@ namespace mpcq {
 // read round trip: ~450 cycles of an ~1,800-cycle tail iteration.)
 __device__ __forceinline__ void wave_sync() { asm volatile("" ::: "memory"); }
 
-// full lane permutations only (quad_perm, row mirrors: every lane has a source), so no "old" operand:
-// the move needs no copy of v into its destination first.  bound_ctrl = true: a lane whose source lane is
-// inactive reads 0, so these moves (and wave_reduce / the scans built on them, here and in mpcq_mimo.hip /
-// mpcq_plant.hip) are only correct under a full EXEC mask.  Every caller runs them in wave-uniform control
-// flow (all 64 lanes active, dead lanes masked by value, not by EXEC).
-template <int CTRL> __device__ __forceinline__ unsigned dpp_u(unsigned v)
-{
-    return (unsigned)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
-}
-template <int CTRL> __device__ __forceinline__ float dpp_t(float v) { return __uint_as_float(dpp_u<CTRL>(__float_as_uint(v))); }
-template <int CTRL> __device__ __forceinline__ double dpp_t(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = dpp_u<CTRL>((unsigned)u), hi = dpp_u<CTRL>((unsigned)(u >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// Whole-wave reduction with a symmetric op: quad swaps, half-row and row mirrors (DPP), then the
-// 16/32-lane swaps of col_reduce.  Every lane ends with the same bits.
-template <typename T, typename F> __device__ __forceinline__ T wave_reduce(T v, F op)
-{
-    v = op(v, dpp_t<0xB1>(v));   // quad_perm [1,0,3,2]
-    v = op(v, dpp_t<0x4E>(v));   // quad_perm [2,3,0,1]
-    v = op(v, dpp_t<0x141>(v));  // row_half_mirror
-    v = op(v, dpp_t<0x140>(v));  // row_mirror
-    return col_reduce(v, op);
-}
 template <typename T> __device__ __forceinline__ T wmax(T v)
 {
     return wave_reduce(v, [](T a, T b) { return tt_fmax(a, b); });
