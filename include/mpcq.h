@@ -74,7 +74,9 @@ extern "C" {
  * it; the contexts it serves have n <= 32 and m <= 64 (mpcq_create refuses larger ones with polish set),
  * and the single-launch entry points (mpcq_mpc_run_device, mpcq_mpc_plants_step_device, mpcq_mimo_*), which
  * cannot fit a second pass, return MPCQ_ERR_ARG on a context whose polish is set.  With polish == 0 every
- * code path, launch and result is what it is without the setting. */
+ * code path, launch and result is what it is without the setting.  A MIMO context (n up to 128) is polished by an
+ * entry point of its own, mpcq_mimo_step_polish_device, on a context whose polish is 0; polish_refine_iter and
+ * delta are its settings too. */
 typedef struct mpcq_settings {
     double rho, sigma, alpha;
     double eps_abs, eps_rel, eps_prim_inf, eps_dual_inf;
@@ -201,8 +203,9 @@ int mpcq_get_info(mpcq_ctx *ctx, int *status, int *iter, double *rho); /* each b
 int mpcq_get_scaling(mpcq_ctx *ctx, double *D, double *E, double *c); /* plant 0: n, m, 1 */
 /* Polish outcome of the last solve (OSQP info->status_polish and the polished residuals; synchronises).
  * Each argument is a host array of `batch` entries and may be NULL.  status_polish: 1 successful,
- * -1 unsuccessful (the ADMM solution was kept), 0 not performed (settings.polish == 0, or the QP did not
- * end MPCQ_SOLVED); n_active: rows of the reduced KKT system (lower-active + upper-active); pri_res,
+ * -1 unsuccessful (the ADMM solution was kept), 0 not performed (settings.polish == 0 and the last step was not
+ * a mpcq_mimo_step_polish_device, or the QP did not end MPCQ_SOLVED); n_active: rows of the reduced KKT system
+ * (lower-active + upper-active); pri_res,
  * dua_res: residuals of the returned solution in the termination norm (unscaled unless
  * scaled_termination), NaN where status_polish == 0. */
 int mpcq_get_polish_info(mpcq_ctx *ctx, int *status_polish, int *n_active, double *pri_res, double *dua_res);
@@ -489,6 +492,26 @@ int mpcq_mimo_setup_plants_device(mpcq_ctx *ctx, int nx, int nu, int ny, int s_r
  * step), U += x[0:n_u] where SOLVED.  yref: device pointer to n_y values, or NULL for 0. */
 int mpcq_mimo_step_device(mpcq_ctx *ctx, const double *X_dev, double *U_dev, const double *yref_dev,
                           void *stream);
+/* One polished controllerStep for every QP: mpcq_mimo_step_device, its kernel, launch and
+ * arithmetic unchanged, then OSQP v0.6 polish.c on every QP that ended MPCQ_SOLVED, in one more kernel on the same
+ * stream; the context keeps a device-to-device copy of U_dev from before the step.  settings.polish stays 0:
+ * settings.delta and settings.polish_refine_iter are read.
+ * Where polish succeeds (OSQP's criterion: both residuals reduced, or one reduced and the other already below
+ * 1e-10) the published x, y (mpcq_get_solution, mpcq_get_dual, mpcq_device_view_get) become the polished point,
+ * the scaled warm state becomes the polished (x^, z^, y^) as OSQP replaces work->x, z, y, and
+ * U_b = U_prev_b + x_b[0:n_u], one fp64 add per component.  Where it does not, or the QP did not end
+ * MPCQ_SOLVED, x, y, the warm state and U are what the plain step left, bit for bit.  status, iter and rho are
+ * always the ADMM's.  A QP with more than n active rows (some bound pair j, n + j both active; a deviation from
+ * OSQP: the reduced system is held for at most n rows) or whose factorisation meets a non-positive pivot is
+ * reported unsuccessful, n_active being the count.
+ * mpcq_get_polish_info serves the call (its buffers are allocated on the first polished step); a plain
+ * mpcq_mimo_step_device or a MIMO setup makes it report "not performed" again.  The sensitivities above the
+ * step's iterate (mpcq_mimo_sensitivity*, mpcq_mimo_step_*) then read the polished iterate.  No atomics: two
+ * calls on equal state give identical bits.
+ * MPCQ_ERR_ORDER: no successful mpcq_mimo_setup_plants_device since the last setup.  MPCQ_ERR_ARG: NULL X / U,
+ * settings.polish set, or `stream` under graph capture.  A refused call writes nothing. */
+int mpcq_mimo_step_polish_device(mpcq_ctx *ctx, const double *X_dev, double *U_dev, const double *yref_dev,
+                                 void *stream);
 
 /* ---- active-set sensitivities of the last MIMO step --------------------------------
  * The definition of mpcq_sensitivity_device above, applied to the last mpcq_mimo_step_device of the context:

@@ -472,6 +472,16 @@ class BatchSolver:
                                                 C.c_void_p(yref_ptr or 0), C.c_void_p(stream or 0)),
                     "mpcq_mimo_step_device")
 
+    def mimo_step_polish_device(self, X_ptr: int, U_ptr: int, yref_ptr: int = 0, stream: int | None = None) -> None:
+        """``mimo_step_device`` followed by OSQP's polish of every SOLVED QP on the same stream (DESIGN.md 4.16;
+        ``settings.polish`` stays 0): where polish succeeds the solution, the dual, the warm state and the applied
+        move U = U_prev + x[:, :nu] are the polished point's, elsewhere the plain step's.  ``polish_info()`` reports
+        the outcome; asynchronous."""
+        self.solve_count += 1
+        _capi.check(lib().mpcq_mimo_step_polish_device(self._ctx, C.c_void_p(X_ptr), C.c_void_p(U_ptr),
+                                                       C.c_void_p(yref_ptr or 0), C.c_void_p(stream or 0)),
+                    "mpcq_mimo_step_polish_device")
+
     # -- active-set sensitivities of the last MIMO step (mpcq_mimo_sensitivity*, mpcq_mimo_step_*; DESIGN.md 4.15)
     def mimo_sensitivity(self, g=None, n_rhs: int | None = None):
         """(gq, gu, n_active) of the last ``mimo_step_device``: ``g`` of shape (batch, n_rhs, n) (or (batch, n) for one

@@ -26,6 +26,7 @@ EXPORTS = (
     "mpcq_sensitivity_device", "mpcq_sensitivity", "mpcq_mpc_step_gains_device", "mpcq_mpc_step_gains",
     "mpcq_sensitivity_data_device", "mpcq_sensitivity_data", "mpcq_condense_vjp_device", "mpcq_condense_vjp",
     "mpcq_mimo_sensitivity_device", "mpcq_mimo_sensitivity", "mpcq_mimo_step_vjp_device", "mpcq_mimo_step_gains_device",
+    "mpcq_mimo_step_polish_device",
 )
 # The symbols whose names follow OSQP's capitals (osqp_update_P_A).  They are kept apart from EXPORTS because the
 # header scan of tests/test_abi.py, which EXPORTS must equal, reads lower-case names only; lib() binds them with
@@ -107,6 +108,7 @@ def lib() -> C.CDLL:
         "mpcq_get_polish_info": (C.c_int, [vp, ip, ip, dp, dp]),
         "mpcq_mimo_setup_plants_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 9 + [vp]),
         "mpcq_mimo_step_device": (C.c_int, [vp, vp, vp, vp, vp]),
+        "mpcq_mimo_step_polish_device": (C.c_int, [vp, vp, vp, vp, vp]),
         "mpcq_mimo_sensitivity_device": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp]),
         "mpcq_mimo_sensitivity": (C.c_int, [vp, dp, C.c_int, dp, dp, ip]),
         "mpcq_mimo_step_vjp_device": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),

@@ -225,10 +225,11 @@ struct mpcq_ctx {
     struct { const double *Ad, *Bd, *Cd, *K, *Q, *R, *RD; int nx, s_rows; } pord_key{};
     bool ord_clean = false;  // the order's bin counters are zero (an ordered phase-0 launch clears them)
     // settings.polish (mpcq_polish.hip): status_polish and the reduced system's rows per QP, the returned
-    // solution's (primal, dual) residual pairs; allocated only when polish is set.  pol_valid: the last solve
-    // filled them (mpcq_get_polish_info reports "not performed" otherwise)
+    // solution's (primal, dual) residual pairs; allocated only when polish is set, or by the first
+    // mpcq_mimo_step_polish_device (mpcq_mimo_polish.hip), which also keeps the caller's U from before the step in
+    // d_mimo_Uprev.  pol_valid: the last solve filled them (mpcq_get_polish_info reports "not performed" otherwise)
     DevBuf<int> d_pol_status, d_pol_nact;
-    DevBuf<double> d_pol_res;
+    DevBuf<double> d_pol_res, d_mimo_Uprev;
     bool pol_valid = false;
     // active-set sensitivities (mpcq_sens.hip).  sens_ok: the warm state and d_l, d_u are those of a solve that
     // mpcq_sensitivity* serves (set by launch_solve outside a stream run; cleared by every setup, data update,

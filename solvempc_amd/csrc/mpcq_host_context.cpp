@@ -334,7 +334,7 @@ int mpcq_get_polish_info(mpcq_ctx *c, int *status_polish, int *n_active, double 
     int rc = check_ctx(c, kAnySetup);
     if (rc) return rc;
     const size_t B = c->dims.batch;
-    if (!c->set.polish || !c->pol_valid) {  // not performed
+    if (!c->pol_valid) {  // not performed (set only by a polish launch: settings.polish, mpcq_mimo_step_polish_device)
         HIPCHK(hipStreamSynchronize(c->last));
         for (size_t b = 0; b < B; b++) {
             if (status_polish) status_polish[b] = 0;

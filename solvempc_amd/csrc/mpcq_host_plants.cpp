@@ -364,6 +364,7 @@ int mpcq_mimo_setup_plants_device(mpcq_ctx *c, int nx, int nu, int ny, int s_row
     c->mode = mpcq_ctx::Mode::None;
     c->sens_ok = false;
     c->mimo_stepped = false;
+    c->pol_valid = false;
     c->gen++;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(c->d_flags, 0, 4, s));
@@ -449,6 +450,45 @@ int mpcq_mimo_step_device(mpcq_ctx *c, const double *X, double *U, const double 
     c->last = s;
     c->fresh = false;
     c->mimo_stepped = true;
+    c->pol_valid = false;
+    return MPCQ_OK;
+}
+
+int mpcq_mimo_step_polish_device(mpcq_ctx *c, const double *X, double *U, const double *yref, void *stream)
+{
+    const char *fn = "mpcq_mimo_step_polish_device";
+    int rc = check_ctx(c, kNone);
+    if (rc) return rc;
+    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal(fn));
+    if (c->mode != mpcq_ctx::Mode::Mimo) return fail(MPCQ_ERR_ORDER, "mpcq_mimo_setup_plants_device has not succeeded");
+    if (!X || !U) return fail(MPCQ_ERR_ARG, "null X/U");
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = refuse_capture(fn, s))) return rc;
+    const size_t B = c->dims.batch, nu = c->mimo_nu;
+    if ((rc = c->d_pol_status.alloc(4 * B)) || (rc = c->d_pol_nact.alloc(4 * B)) || (rc = c->d_pol_res.alloc(8 * 2 * B)) ||
+        (rc = c->d_mimo_Uprev.grow(8 * B * nu, s, "mimo polish staging")))
+        return rc;
+    HIPCHK(hipMemcpyAsync(c->d_mimo_Uprev, U, 8 * B * nu, hipMemcpyDeviceToDevice, s));
+    if ((rc = mpcq_mimo_step_device(c, X, U, yref, stream))) return rc;
+    mpcq::MimoPolishArgs a{};
+    a.batch = c->dims.batch;
+    a.N = c->mimo_N; a.nx = c->mimo_nx; a.nu = c->mimo_nu; a.ny = c->mimo_ny;
+    a.ops_stride = (size_t)mpcq::MimoLayout::make(a.N, a.nx, a.nu, a.ny).total;
+    a.ops = c->d_mimo;
+    a.q = c->d_q; a.u = c->d_u;
+    a.xs = (double *)c->d_xs; a.zs = (double *)c->d_zs; a.ys = (double *)c->d_ys;
+    a.status = c->d_status;
+    a.x = c->d_x; a.y = c->d_y;
+    a.U_prev = c->d_mimo_Uprev; a.U = U;
+    a.pol_status = c->d_pol_status; a.pol_nact = c->d_pol_nact; a.pol_res = c->d_pol_res;
+    a.delta = c->set.delta;
+    a.refine = c->set.polish_refine_iter;
+    a.scaled_termination = c->set.scaled_termination;
+    hipError_t err = hipSuccess;
+    const int lr = mpcq_internal_mimo_polish_launch(&a, c->cus, s, &err);
+    if (lr == -1) return fail(MPCQ_ERR_ARG, "mimo polish: shape beyond the kernel's capacity");
+    if (lr) return fail(MPCQ_ERR_HIP, std::string("mimo polish kernel launch failed: ") + hipGetErrorString(err));
+    c->pol_valid = true;
     return MPCQ_OK;
 }
 

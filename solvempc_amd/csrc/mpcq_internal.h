@@ -438,6 +438,24 @@ struct MimoSensArgs {
     double delta;
     int refine;
 };
+
+// Arguments of polish_mimo_kernel (mpcq_mimo_polish.hip): OSQP's polish of the MIMO step just enqueued, one workgroup
+// per QP, fp64.  Written where polish succeeds: x, y, the warm state and U; always: the three pol_* arrays.
+struct MimoPolishArgs {
+    int batch, N, nx, nu, ny;
+    size_t ops_stride;
+    const double *ops;          // [plant] MimoLayout
+    const double *q, *u;        // [batch] n, 2n: the step's unscaled q, u (MimoArgs::q_out, u_out)
+    double *xs, *zs, *ys;       // [batch] n, 2n, 2n: the step's final scaled iterate
+    const int *status;          // [batch] the ADMM's status: only MPCQ_SOLVED QPs are polished
+    double *x, *y;              // [batch] n, 2n: the published solution
+    const double *U_prev;       // [batch] nu: the caller's U from before the step
+    double *U;                  // [batch] nu: U = U_prev + x[0:nu] where polish succeeds
+    int *pol_status, *pol_nact; // [batch] OSQP status_polish (1, -1, 0), rows of the reduced system
+    double *pol_res;            // [batch][2] primal, dual residual of the returned solution (NaN: not performed)
+    double delta;
+    int refine, scaled_termination;
+};
 }  // namespace mpcq
 
 namespace mpcq {
@@ -749,6 +767,10 @@ int mpcq_internal_mimo_solve_launch(const mpcq::MimoArgs *a, hipStream_t s);
 // dynamic LDS bytes for n variables: mpcq_internal_mimo_sens_lds.
 int mpcq_internal_mimo_sens_launch(const mpcq::MimoSensArgs *a, int cus, hipStream_t s, hipError_t *err);
 size_t mpcq_internal_mimo_sens_lds(int n);
+// OSQP polish of every SOLVED QP of the last MIMO step (mpcq_mimo_polish.hip; every shape the MIMO setup accepts),
+// same return codes; its dynamic LDS bytes for n variables.
+int mpcq_internal_mimo_polish_launch(const mpcq::MimoPolishArgs *a, int cus, hipStream_t s, hipError_t *err);
+size_t mpcq_internal_mimo_polish_lds(int n);
 // One pass per batch of distinct SISO plants (mpcq_plant.hip): condensing + setup + one
 // controllerStep per plant, two plants per wave.  0 launched, -1 unsupported shape, -2 HIP error.
 int mpcq_internal_plant_step_launch(const mpcq::PlantStepArgs *a, int is_f32, hipStream_t s);

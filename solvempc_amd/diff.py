@@ -136,7 +136,7 @@ class _QpSolution(torch.autograd.Function):
 
 class _MimoSolution(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, solver, X, U, yref):
+    def forward(ctx, solver, polish, X, U, yref):
         B, n = solver.batch, solver.n
         nx, nu, ny = solver.nx, getattr(solver, "nu", 0), getattr(solver, "ny", 0)
         if not (nu and ny):
@@ -146,7 +146,8 @@ class _MimoSolution(torch.autograd.Function):
                 raise ValueError(f"mimo_solution: {name} must be a device fp64 tensor of shape {shape}")
         Xc, Uc, yc = X.detach().contiguous(), U.detach().clone().contiguous(), yref.detach().contiguous()
         stream = torch.cuda.current_stream(X.device).cuda_stream
-        solver.mimo_step_device(Xc.data_ptr(), Uc.data_ptr(), yc.data_ptr(), stream)
+        step = solver.mimo_step_polish_device if polish else solver.mimo_step_device
+        step(Xc.data_ptr(), Uc.data_ptr(), yc.data_ptr(), stream)
         view = solver.device_view()
         x = torch.as_tensor(_DevArray(view["x"], (B, n), "<f8"), device=X.device).clone()
         status = torch.as_tensor(_DevArray(view["status"], (B,), "<i4"), device=X.device).clone()
@@ -167,7 +168,7 @@ class _MimoSolution(torch.autograd.Function):
         dX, dU, dy = new(B, nx), new(B, nu), new(B, ny)
         stream = torch.cuda.current_stream(g.device).cuda_stream
         solver.mimo_step_vjp_device(g.data_ptr(), 1, dX.data_ptr(), dU.data_ptr(), dy.data_ptr(), 0, stream)
-        return None, dX, dU, dy.sum(dim=0)  # (yref is one vector for the whole batch)
+        return None, None, dX, dU, dy.sum(dim=0)  # (yref is one vector for the whole batch)
 
 
 _PLANT = ("Ad", "Bd", "Cd", "K", "Q", "R", "RD")
@@ -270,15 +271,17 @@ def mpc_plant_solution(solver, Ad, Bd, Cd, K, Q, R, RD, X, U, ref, s_rows=10, se
     return _MpcPlantSolution.apply(solver, s_rows, setup, Ad, Bd, Cd, K, Q, R, RD, X, U, ref)
 
 
-def mimo_solution(solver, X, U, yref):
+def mimo_solution(solver, X, U, yref, polish=False):
     """One MIMO MPC step ``solver.mimo_step_device`` (after ``mimo_setup_plants_device``) on device fp64 tensors
     X (batch, nx), U (batch, nu), yref (ny,), differentiable with respect to all three.  Returns ``(x, status)`` as
     ``mpc_solution`` does; the caller's U is left alone (the applied move is x[:, :nu]).  Backward is one
     ``BatchSolver.mimo_step_vjp_device`` call on the incoming cotangent (solvempc_amd/csrc/mpcq_mimo_sens.hip;
     DESIGN.md 4.15), the per-QP gradients of yref summed over the batch: the gradient of the QP's optimum at the
-    active set of the step's final iterate, zero for a QP that did not end SOLVED.  ``backward`` must run before
-    the solver solves again."""
-    return _MimoSolution.apply(solver, X, U, yref)
+    active set of the step's final iterate, zero for a QP that did not end SOLVED.  With ``polish`` the forward pass
+    is ``solver.mimo_step_polish_device``: x is the polished point where polish succeeds, and the
+    unchanged backward pass then reads the polished iterate.  ``backward`` must run before the solver solves
+    again."""
+    return _MimoSolution.apply(solver, bool(polish), X, U, yref)
 
 
 def qp_solution(solver, P, A, q, l, u, setup=True):
