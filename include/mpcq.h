@@ -552,6 +552,41 @@ int mpcq_mimo_step_vjp_device(mpcq_ctx *ctx, const double *g_dev, int n_rhs, dou
 int mpcq_mimo_step_gains_device(mpcq_ctx *ctx, double *dX_dev, double *dU_dev, double *dyref_dev, int *n_active_dev,
                                 void *stream);
 
+/* ---- the last MIMO step differentiated in the plant model, the weights and the constraint data
+ * The nine plant arrays are those mpcq_mimo_setup_plants_device read (device, fp64, plant-major; the caller vouches
+ * that they are unchanged); n_x, n_u, n_y, N and s_rows are the context's own from that setup.  X_dev (batch*n_x) is
+ * the X of the context's last MIMO step, U_prev_dev (batch*n_u) the U from before that step (which the step
+ * overwrites), yref_dev (n_y, or NULL for 0) that step's yref.  g_dev: batch*n cotangents of x*, or NULL for e_0.
+ * Per QP, with (gq, w = gu, n_active) what mpcq_mimo_sensitivity_device(g, n_rhs = 1) returns for this step, x and y
+ * the published solution and dual, and y_a = y on the rows of the active set that call uses (polish's rule on the
+ * step's final scaled iterate), 0 elsewhere, the operator cotangents are
+ *   gP = 1/2 (gq x' + x gq')     gA = y_a gq' - w x'
+ *   gFx = gq X'    gFu = gq U_prev'    gFr = gq (1_N (x) yref)'    gSbar = w X'    gKu = w U_prev'    gW0 = w
+ * and the outputs are these pulled back through the MIMO condensing as oracle/mpc_mimo.c states it
+ * (P = (H1 + H1')/2, ...): gAd batch*n_x*n_x, gBd batch*n_x*n_u, gCd batch*n_y*n_x, gQ batch*n_y*n_y, gR, gRD
+ * batch*n_u*n_u, gK batch*n_u*n_x, gK0 batch*n_u*n_u, gw0 batch*n_u.  Q, R and RD are treated as general matrices:
+ * a caller with a symmetric parametrisation symmetrises.  No n x n object is formed: every term is a sum over the
+ * horizon of small outer products (the factored form of DESIGN.md 4.17).  A QP with n_active = -1 gets all-zero
+ * outputs.  Each output may be NULL, not all; an output's bits do not depend on which others are NULL.
+ * Two kernels on `stream`: the sensitivity solve into staging the context owns (allocated on the first call), then
+ * the pull-back.  Read-only on the context, ordered after the context's last stream (an event) with the context's
+ * next step ordered after it, as mpcq_mimo_sensitivity_device; after mpcq_mimo_step_polish_device the polished
+ * iterate is read.  No atomics, sums in a fixed order: two calls give identical bits.
+ * MPCQ_ERR_ORDER: no setup; no mpcq_mimo_step_device since the last MIMO setup.  MPCQ_ERR_ARG: a context whose last
+ * setup is not a MIMO one; a NULL plant array, X or U_prev; every output NULL; `stream` under graph capture.  A
+ * refused call writes nothing. */
+int mpcq_mimo_plant_vjp_device(mpcq_ctx *ctx, const double *g_dev, const double *Ad, const double *Bd, const double *Cd,
+                               const double *Q, const double *R, const double *RD, const double *K, const double *K0,
+                               const double *w0, const double *X_dev, const double *U_prev_dev, const double *yref_dev,
+                               double *gAd, double *gBd, double *gCd, double *gQ, double *gR, double *gRD, double *gK,
+                               double *gK0, double *gw0, int *n_active_dev, void *stream);
+/* Host-memory form (copies in/out, synchronises); the same arrays on the host. */
+int mpcq_mimo_plant_vjp(mpcq_ctx *ctx, const double *g, const double *Ad, const double *Bd, const double *Cd,
+                        const double *Q, const double *R, const double *RD, const double *K, const double *K0,
+                        const double *w0, const double *X, const double *U_prev, const double *yref, double *gAd,
+                        double *gBd, double *gCd, double *gQ, double *gR, double *gRD, double *gK, double *gK0, double *gw0,
+                        int *n_active);
+
 /* Last HIP error string of this thread (static storage). */
 const char *mpcq_last_error(void);
 

@@ -546,6 +546,45 @@ class BatchSolver:
         stream.synchronize()
         return dX.cpu().numpy(), dU.cpu().numpy(), dy.cpu().numpy(), na.cpu().numpy()
 
+    # -- the last MIMO step differentiated in the plant data (mpcq_mimo_plant_vjp*)
+    MIMO_PLANT_KEYS = ("Ad", "Bd", "Cd", "Q", "R", "RD", "K", "K0", "w0")
+
+    def mimo_plant_vjp_device(self, g_ptr: int, plant_ptrs, X_ptr: int, U_prev_ptr: int, yref_ptr: int, grad_ptrs,
+                              n_active_ptr: int = 0, stream: int | None = None) -> None:
+        """The cotangent at g_ptr (batch, n; 0: e_0) of the last MIMO step's solution pulled back to the plant data,
+        on device-resident fp64 buffers: ``plant_ptrs`` are the nine arrays ``mimo_setup_plants_device`` read, in
+        its order (``MIMO_PLANT_KEYS``), ``grad_ptrs`` nine outputs of the same shapes (any may be 0, not all);
+        X_ptr is the step's X, U_prev_ptr the U from before the step, yref_ptr its yref (0: none).  Asynchronous on
+        ``stream``, ordered after the solver's last stream."""
+        plant_ptrs, grad_ptrs = list(plant_ptrs), list(grad_ptrs)
+        if len(plant_ptrs) != 9 or len(grad_ptrs) != 9:
+            raise ValueError("mimo_plant_vjp_device: nine plant pointers and nine gradient pointers (MIMO_PLANT_KEYS)")
+        ptrs = [C.c_void_p(p or 0) for p in [g_ptr] + plant_ptrs + [X_ptr, U_prev_ptr, yref_ptr] + grad_ptrs
+                + [n_active_ptr]]
+        _capi.check(lib().mpcq_mimo_plant_vjp_device(self._ctx, *ptrs, C.c_void_p(stream or 0)),
+                    "mpcq_mimo_plant_vjp_device")
+
+    def mimo_plant_vjp(self, plant: dict, X, U_prev, yref=None, g=None) -> dict:
+        """Host-memory form: ``plant`` maps ``MIMO_PLANT_KEYS`` to arrays with a leading batch axis, X (batch, nx),
+        U_prev (batch, nu), yref (ny) or None, g (batch, n) or None for e_0.  Returns a dict of the nine gradients
+        under the same keys and ``n_active`` (batch; -1 and zero gradients where no sensitivity exists)."""
+        keep = [np.ascontiguousarray(_c64(plant[k])) for k in self.MIMO_PLANT_KEYS]
+        X, U_prev = np.ascontiguousarray(_c64(X)), np.ascontiguousarray(_c64(U_prev))
+        yref = None if yref is None else np.ascontiguousarray(_c64(yref))
+        g = None if g is None else np.ascontiguousarray(_c64(g).reshape(self.batch, self.n))
+        for a in keep + [X, U_prev]:
+            if a.shape[0] != self.batch:
+                raise ValueError("mimo_plant_vjp: every array carries a leading batch axis")
+        out = [np.empty_like(a) for a in keep]
+        na = np.empty(self.batch, dtype=np.int32)
+        opt = lambda a: None if a is None else _dp(a)
+        _capi.check(lib().mpcq_mimo_plant_vjp(self._ctx, opt(g), *[_dp(a) for a in keep], _dp(X), _dp(U_prev), opt(yref),
+                                              *[_dp(a) for a in out], na.ctypes.data_as(C.POINTER(C.c_int))),
+                    "mpcq_mimo_plant_vjp")
+        res = dict(zip(self.MIMO_PLANT_KEYS, out))
+        res["n_active"] = na
+        return res
+
     def mpc_step_device(self, X_ptr: int, U_ptr: int, xref: float = 0.0, stream: int | None = None) -> None:
         """Same on device-resident fp64 buffers (e.g. torch tensors' data_ptr()); asynchronous."""
         self.solve_count += 1

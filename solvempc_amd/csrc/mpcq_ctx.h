@@ -201,6 +201,9 @@ struct mpcq_ctx {
     int mimo_N = 0, mimo_nx = 0, mimo_nu = 0, mimo_ny = 0, mimo_srows = 0, mimo_diag_k0 = 0;
     bool mimo_only = false;  // n > 32 or m > 64 per plant: only the MIMO entry points serve it
     bool mimo_stepped = false;  // a mpcq_mimo_step_device since the last MIMO setup (mpcq_mimo_sensitivity* needs one)
+    // mpcq_mimo_plant_vjp*: mimo_sens_kernel's (gq, gu, n_active) for the call's g, which mimo_plant_vjp_kernel reads
+    // (batch*n, batch*2n doubles, then batch ints; allocated on first use)
+    DevBuf<double> d_mimo_pv;
     // receding-horizon stream counters (mpcq_mpc_run_device): per-QP iterations and unsolved steps
     DevBuf<int> d_it_acc, d_uns_acc;
     bool stream_acc = false;  // launches made inside mpcq_mpc_run_device accumulate into them

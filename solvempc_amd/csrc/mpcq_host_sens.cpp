@@ -141,6 +141,73 @@ int mimo_sens_enqueue(mpcq_ctx *c, const double *g, int n_rhs, double *gq, doubl
     return order_last_after(c, s);
 }
 
+// ---- the MIMO step pulled back to the plant data (mpcq_mimo_plant_vjp.hip; include/mpcq.h)
+// The nine plant arrays in the header's order (Ad, Bd, Cd, Q, R, RD, K, K0, w0) and their element counts per plant
+struct MimoPlantPtrs {
+    const double *in[9];
+    double *out[9];
+};
+
+void mimo_plant_sizes(const mpcq_ctx *c, size_t sz[9])
+{
+    const size_t nx = c->mimo_nx, nu = c->mimo_nu, ny = c->mimo_ny;
+    const size_t s[9] = {nx * nx, nx * nu, ny * nx, ny * ny, nu * nu, nu * nu, nu * nx, nu * nu, nu};
+    std::copy(s, s + 9, sz);
+}
+
+// The refusals of include/mpcq.h, before anything is allocated, enqueued or written
+int mimo_plant_vjp_check(mpcq_ctx *c, const char *fn, const MimoPlantPtrs &p, const double *X, const double *U_prev,
+                         const int *n_active, hipStream_t s)
+{
+    int rc = check_ctx(c, kNone);
+    if (rc) return rc;
+    if (c->mode == mpcq_ctx::Mode::None)
+        return fail(MPCQ_ERR_ORDER, std::string(fn) + ": mpcq_mimo_setup_plants_device has not succeeded");
+    if (c->mode != mpcq_ctx::Mode::Mimo)
+        return fail(MPCQ_ERR_ARG, std::string(fn) + ": the context was not set up by mpcq_mimo_setup_plants_device");
+    if (!c->mimo_stepped)
+        return fail(MPCQ_ERR_ORDER, std::string(fn) + ": needs a mpcq_mimo_step_device since the last setup");
+    bool any_out = n_active != nullptr;
+    for (int k = 0; k < 9; k++) {
+        if (!p.in[k]) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null plant array");
+        any_out = any_out || p.out[k];
+    }
+    if (!X || !U_prev) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null X / U_prev");
+    if (!any_out) return fail(MPCQ_ERR_ARG, std::string(fn) + ": every output is NULL");
+    return refuse_capture(fn, s);
+}
+
+// mimo_sens_kernel (n_rhs = 1) into the context's staging, then mimo_plant_vjp_kernel, both on s
+int mimo_plant_vjp_enqueue(mpcq_ctx *c, const double *g, const MimoPlantPtrs &p, const double *X, const double *U_prev,
+                           const double *yref, int *n_active, hipStream_t s)
+{
+    const size_t B = c->dims.batch, n = c->dims.n, m = c->dims.m;
+    if (int rc = c->d_mimo_pv.alloc(8 * (B * (n + m) + (B + 1) / 2), "mimo plant-gradient staging")) return rc;
+    double *gq = c->d_mimo_pv, *gu = gq + B * n;
+    int *nact = (int *)(gu + B * m);
+    if (int rc = mimo_sens_enqueue(c, g, 1, gq, gu, nullptr, nullptr, nullptr, nact, s)) return rc;
+    mpcq::MimoPlantVjpArgs a{};
+    a.batch = c->dims.batch;
+    a.N = c->mimo_N; a.nx = c->mimo_nx; a.nu = c->mimo_nu; a.ny = c->mimo_ny; a.s_rows = c->mimo_srows;
+    a.ops_stride = (size_t)mpcq::MimoLayout::make(a.N, a.nx, a.nu, a.ny).total;
+    a.ops = c->d_mimo;
+    a.u = c->d_u;
+    a.zs = (const double *)c->d_zs;
+    a.ys = (const double *)c->d_ys;
+    a.x = c->d_x; a.y = c->d_y;
+    a.gq = gq; a.gu = gu; a.nact = nact;
+    a.Ad = p.in[0]; a.Bd = p.in[1]; a.Cd = p.in[2]; a.Q = p.in[3];
+    a.X = X; a.U_prev = U_prev; a.yref = yref;
+    a.gAd = p.out[0]; a.gBd = p.out[1]; a.gCd = p.out[2]; a.gQ = p.out[3]; a.gR = p.out[4]; a.gRD = p.out[5];
+    a.gK = p.out[6]; a.gK0 = p.out[7]; a.gw0 = p.out[8];
+    a.n_active = n_active;
+    hipError_t err = hipSuccess;
+    const int lr = mpcq_internal_mimo_plant_vjp_launch(&a, c->cus, s, &err);
+    if (lr == -1) return fail(MPCQ_ERR_ARG, "mimo plant gradients: shape beyond the kernel's capacity");
+    if (lr) return fail(MPCQ_ERR_HIP, std::string("mimo plant-gradient kernel launch failed: ") + hipGetErrorString(err));
+    return order_last_after(c, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -287,6 +354,61 @@ int mpcq_mimo_step_gains_device(mpcq_ctx *c, double *dX, double *dU, double *dyr
                              dX || dU || dyref || n_active, (hipStream_t)stream);
     if (rc) return rc;
     return mimo_sens_enqueue(c, nullptr, c->mimo_nu, nullptr, nullptr, dX, dU, dyref, n_active, (hipStream_t)stream);
+}
+
+int mpcq_mimo_plant_vjp_device(mpcq_ctx *c, const double *g, const double *Ad, const double *Bd, const double *Cd,
+                               const double *Q, const double *R, const double *RD, const double *K, const double *K0,
+                               const double *w0, const double *X, const double *U_prev, const double *yref, double *gAd,
+                               double *gBd, double *gCd, double *gQ, double *gR, double *gRD, double *gK, double *gK0,
+                               double *gw0, int *n_active, void *stream)
+{
+    const MimoPlantPtrs p{{Ad, Bd, Cd, Q, R, RD, K, K0, w0}, {gAd, gBd, gCd, gQ, gR, gRD, gK, gK0, gw0}};
+    int rc = mimo_plant_vjp_check(c, "mpcq_mimo_plant_vjp_device", p, X, U_prev, n_active, (hipStream_t)stream);
+    if (rc) return rc;
+    return mimo_plant_vjp_enqueue(c, g, p, X, U_prev, yref, n_active, (hipStream_t)stream);
+}
+
+int mpcq_mimo_plant_vjp(mpcq_ctx *c, const double *g, const double *Ad, const double *Bd, const double *Cd,
+                        const double *Q, const double *R, const double *RD, const double *K, const double *K0,
+                        const double *w0, const double *X, const double *U_prev, const double *yref, double *gAd,
+                        double *gBd, double *gCd, double *gQ, double *gR, double *gRD, double *gK, double *gK0, double *gw0,
+                        int *n_active)
+{
+    const MimoPlantPtrs h{{Ad, Bd, Cd, Q, R, RD, K, K0, w0}, {gAd, gBd, gCd, gQ, gR, gRD, gK, gK0, gw0}};
+    int rc = mimo_plant_vjp_check(c, "mpcq_mimo_plant_vjp", h, X, U_prev, n_active, c ? c->last : nullptr);
+    if (rc) return rc;
+    const size_t B = c->dims.batch, n = c->dims.n, nx = c->mimo_nx, nu = c->mimo_nu, ny = c->mimo_ny;
+    size_t sz[9], per = 0;
+    mimo_plant_sizes(c, sz);
+    for (size_t k : sz) per += k;
+    // staging of this call alone: g (B n), the plant arrays and their gradients (B per each), X, U_prev, yref, B ints
+    DevBuf<double> d;
+    if ((rc = d.alloc(8 * (B * (n + 2 * per + nx + nu) + ny + (B + 1) / 2), "mimo plant-gradient staging"))) return rc;
+    struct Drain {  // (the stream is waited for, whatever the outcome, before the staging goes away)
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{c->last};
+    double *o = d, *dg = o;
+    o += B * n;
+    MimoPlantPtrs p{};
+    for (int k = 0; k < 9; k++) {
+        if ((rc = h2d(o, h.in[k], 8 * B * sz[k], c->last))) return rc;
+        p.in[k] = o;
+        o += B * sz[k];
+    }
+    for (int k = 0; k < 9; k++) {
+        p.out[k] = h.out[k] ? o : nullptr;
+        o += B * sz[k];
+    }
+    double *dX = o, *dU = dX + B * nx, *dy = dU + B * nu;
+    int *dna = (int *)(dy + ny);
+    if ((g && (rc = h2d(dg, g, 8 * B * n, c->last))) || (rc = h2d(dX, X, 8 * B * nx, c->last)) ||
+        (rc = h2d(dU, U_prev, 8 * B * nu, c->last)) || (yref && (rc = h2d(dy, yref, 8 * ny, c->last))))
+        return rc;
+    if ((rc = mimo_plant_vjp_enqueue(c, g ? dg : nullptr, p, dX, dU, yref ? dy : nullptr, dna, c->last))) return rc;
+    for (int k = 0; k < 9; k++)
+        if ((rc = d2h(c, h.out[k], p.out[k], 8 * B * sz[k]))) return rc;
+    return d2h(c, n_active, dna, 4 * B);
 }
 
 }  // extern "C"

@@ -456,6 +456,25 @@ struct MimoPolishArgs {
     double delta;
     int refine, scaled_termination;
 };
+
+// Arguments of mimo_plant_vjp_kernel (mpcq_mimo_plant_vjp.hip): the cotangents of the last MIMO step's QP data
+// pulled back through the MIMO condensing to the plant data, one workgroup per plant, fp64.
+// Everything of the context is read-only.
+struct MimoPlantVjpArgs {
+    int batch, N, nx, nu, ny, s_rows;
+    size_t ops_stride;
+    const double *ops;          // [plant] MimoLayout (E is read: the active set's rule)
+    const double *u;            // [batch] 2n: the step's unscaled upper bounds (MimoArgs::u_out)
+    const double *zs, *ys;      // [batch] 2n: the step's final scaled iterate
+    const double *x, *y;        // [batch] n, 2n: the published solution and dual
+    const double *gq, *gu;      // [batch] n, 2n: mimo_sens_kernel's gradients for this call's g (n_rhs = 1)
+    const int *nact;            // [batch] its n_active: -1 where no sensitivity exists (all-zero outputs)
+    const double *Ad, *Bd, *Cd, *Q;  // [plant] nx*nx, nx*nu, ny*nx, ny*ny (the other plant arrays enter linearly)
+    const double *X, *U_prev;   // [batch] nx, nu: the step's X and the U from before it
+    const double *yref;         // ny, or null: 0
+    double *gAd, *gBd, *gCd, *gQ, *gR, *gRD, *gK, *gK0, *gw0;  // [plant] shapes of the plant data; each may be null
+    int *n_active;              // [batch] copy of nact (or null)
+};
 }  // namespace mpcq
 
 namespace mpcq {
@@ -771,6 +790,10 @@ size_t mpcq_internal_mimo_sens_lds(int n);
 // same return codes; its dynamic LDS bytes for n variables.
 int mpcq_internal_mimo_polish_launch(const mpcq::MimoPolishArgs *a, int cus, hipStream_t s, hipError_t *err);
 size_t mpcq_internal_mimo_polish_lds(int n);
+// The last MIMO step's cotangents pulled back to the plant data (mpcq_mimo_plant_vjp.hip; every shape the MIMO
+// setup accepts), same return codes; its dynamic LDS bytes for the call's N, nx, nu, ny.
+int mpcq_internal_mimo_plant_vjp_launch(const mpcq::MimoPlantVjpArgs *a, int cus, hipStream_t s, hipError_t *err);
+size_t mpcq_internal_mimo_plant_vjp_lds(int N, int nx, int nu, int ny);
 // One pass per batch of distinct SISO plants (mpcq_plant.hip): condensing + setup + one
 // controllerStep per plant, two plants per wave.  0 launched, -1 unsupported shape, -2 HIP error.
 int mpcq_internal_plant_step_launch(const mpcq::PlantStepArgs *a, int is_f32, hipStream_t s);

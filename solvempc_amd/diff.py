@@ -171,6 +171,66 @@ class _MimoSolution(torch.autograd.Function):
         return None, None, dX, dU, dy.sum(dim=0)  # (yref is one vector for the whole batch)
 
 
+_MIMO_PLANT = ("Ad", "Bd", "Cd", "Q", "R", "RD", "K", "K0", "w0")
+
+
+class _MimoPlantSolution(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, s_rows, polish, setup, Ad, Bd, Cd, Q, R, RD, K, K0, w0, X, U, yref):
+        B, n, m = solver.batch, solver.n, solver.m
+        if solver.n_plants != B or m != 2 * n:
+            raise ValueError("mimo_plant_solution: the solver must have n_plants == batch and m == 2 n (the MIMO shape)")
+        nx, nu = (int(Bd.shape[1]), int(Bd.shape[2])) if Bd.dim() == 3 else (0, 0)
+        ny = int(Cd.shape[1]) if Cd.dim() == 3 else 0
+        shapes = {"Ad": (B, nx, nx), "Bd": (B, nx, nu), "Cd": (B, ny, nx), "Q": (B, ny, ny), "R": (B, nu, nu),
+                  "RD": (B, nu, nu), "K": (B, nu, nx), "K0": (B, nu, nu), "w0": (B, nu), "X": (B, nx), "U": (B, nu),
+                  "yref": (ny,)}
+        given = dict(zip(_MIMO_PLANT + ("X", "U", "yref"), (Ad, Bd, Cd, Q, R, RD, K, K0, w0, X, U, yref)))
+        for name, t in given.items():
+            if not (t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == shapes[name]):
+                raise ValueError(f"mimo_plant_solution: {name} must be a device fp64 tensor of shape {shapes[name]}")
+        plant = [given[k].detach().contiguous() for k in _MIMO_PLANT]
+        Xc, U0, yc = X.detach().contiguous(), U.detach().contiguous(), yref.detach().contiguous()
+        Uc = U0.clone()  # (the step adds the applied move to its U)
+        stream = torch.cuda.current_stream(X.device).cuda_stream
+        if setup:
+            solver.mimo_setup_plants_device(nx, nu, ny, int(s_rows), *[t.data_ptr() for t in plant], stream=stream)
+        elif (solver.nx, getattr(solver, "nu", 0), getattr(solver, "ny", 0)) != (nx, nu, ny):
+            raise ValueError("mimo_plant_solution: setup=False, but the solver holds no MIMO plants of these dimensions")
+        step = solver.mimo_step_polish_device if polish else solver.mimo_step_device
+        step(Xc.data_ptr(), Uc.data_ptr(), yc.data_ptr(), stream)
+        view = solver.device_view()
+        x = torch.as_tensor(_DevArray(view["x"], (B, n), "<f8"), device=X.device).clone()
+        status = torch.as_tensor(_DevArray(view["status"], (B,), "<i4"), device=X.device).clone()
+        ctx.keep = (plant, Xc, U0, yc, Uc)
+        ctx.solver, ctx.count, ctx.dims = solver, solver.solve_count, (nx, nu, ny)
+        ctx.mark_non_differentiable(status)
+        return x, status
+
+    @staticmethod
+    def backward(ctx, gx, _gstatus):
+        solver = ctx.solver
+        if solver.solve_count != ctx.count:
+            raise RuntimeError("mimo_plant_solution.backward: the solver has solved again since this forward pass, so "
+                               "its state is no longer this solve's; run backward before the next solve")
+        B, (nx, nu, ny), (plant, X, U0, yref, _) = solver.batch, ctx.dims, ctx.keep
+        g = gx.contiguous()
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        grads = [None] * 9
+        if any(ctx.needs_input_grad[4:13]):
+            grads = [torch.empty_like(t) for t in plant]
+            solver.mimo_plant_vjp_device(g.data_ptr(), [t.data_ptr() for t in plant], X.data_ptr(), U0.data_ptr(),
+                                         yref.data_ptr(), [t.data_ptr() for t in grads], 0, stream)
+            grads = [t if need else None for t, need in zip(grads, ctx.needs_input_grad[4:13])]
+        dX = dU = dy = None
+        if any(ctx.needs_input_grad[13:16]):
+            new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=g.device)
+            dX, dU, dy = new(B, nx), new(B, nu), new(B, ny)
+            solver.mimo_step_vjp_device(g.data_ptr(), 1, dX.data_ptr(), dU.data_ptr(), dy.data_ptr(), 0, stream)
+            dy = dy.sum(dim=0)  # (yref is one vector for the whole batch)
+        return (None, None, None, None, *grads, dX, dU, dy)
+
+
 _PLANT = ("Ad", "Bd", "Cd", "K", "Q", "R", "RD")
 
 
@@ -282,6 +342,24 @@ def mimo_solution(solver, X, U, yref, polish=False):
     unchanged backward pass then reads the polished iterate.  ``backward`` must run before the solver solves
     again."""
     return _MimoSolution.apply(solver, bool(polish), X, U, yref)
+
+
+def mimo_plant_solution(solver, Ad, Bd, Cd, Q, R, RD, K, K0, w0, X, U, yref, s_rows, polish=False, setup=True):
+    """One MIMO MPC step as a differentiable function of the plant model (Ad, Bd, Cd), the weights (Q, R, RD) and
+    the constraint data (K, K0, w0) as well as of the step's data: per-plant device fp64 tensors Ad (batch, nx, nx),
+    Bd (batch, nx, nu), Cd (batch, ny, nx), Q (batch, ny, ny), R, RD (batch, nu, nu), K (batch, nu, nx), K0
+    (batch, nu, nu), w0 (batch, nu), and X (batch, nx), U (batch, nu), yref (ny,).  Returns ``(x, status)`` as
+    ``mimo_solution`` does; the caller's U is left alone.
+
+    Forward: ``solver.mimo_setup_plants_device`` on the tensors' own memory (with ``setup=False`` the caller vouches
+    that the solver already holds these plants, and only the step runs), then ``mimo_step_device``, or
+    ``mimo_step_polish_device`` with ``polish``, on a private copy of U.  Backward: one
+    ``BatchSolver.mimo_plant_vjp_device`` call for the nine plant gradients (no operator cotangent
+    is materialised), and ``mimo_step_vjp_device`` for X, U and yref only where one of them requires a gradient.
+    Q, R and RD are differentiated as general matrices: parametrise them symmetrically in torch and autograd
+    symmetrises.  The gradient is that of the QP's optimum at the active set of the step's final iterate, zero for
+    a QP that did not end SOLVED.  ``backward`` must run before the solver solves again."""
+    return _MimoPlantSolution.apply(solver, s_rows, bool(polish), setup, Ad, Bd, Cd, Q, R, RD, K, K0, w0, X, U, yref)
 
 
 def qp_solution(solver, P, A, q, l, u, setup=True):
