@@ -260,7 +260,7 @@ int mpcq_mpc_step(mpcq_ctx *ctx, const double *X, double *U, double xref);
  * settings.polish.  q and u are written eagerly on this path (no lazy q/u): mpcq_device_view_get().q and
  * a following mpcq_solve see this step's q even after the caller has overwritten ref_dev.
  * Returns MPCQ_ERR_ARG for a null ref or a non-zero stride < n, otherwise as mpcq_mpc_step_device.
- * Out of scope: mpcq_mpc_plants_step_device and the MIMO entry points (MIMO has yref). */
+ * Out of scope: mpcq_mpc_plants_step_device.  A MIMO context has twins of its own, mpcq_mimo_step_ref*. */
 int mpcq_mpc_step_ref_device(mpcq_ctx *ctx, const double *X_dev, double *U_dev, const double *ref_dev,
                              long long ref_stride, void *stream);
 /* Host-memory form (copies in/out, synchronises), as mpcq_mpc_step is to mpcq_mpc_step_device. */
@@ -512,6 +512,30 @@ int mpcq_mimo_step_device(mpcq_ctx *ctx, const double *X_dev, double *U_dev, con
  * settings.polish set, or `stream` under graph capture.  A refused call writes nothing. */
 int mpcq_mimo_step_polish_device(mpcq_ctx *ctx, const double *X_dev, double *U_dev, const double *yref_dev,
                                  void *stream);
+/* One controllerStep for every QP with its own output reference over the horizon, the MIMO twin of
+ * mpcq_mpc_step_ref_device:
+ *   q_b = Fx X_b + Fu U_b + Fr ref_b,  ref_b[i*n_y + y] = ref_dev[b*ref_stride + i*n_y + y], i < N, y < n_y.
+ * ref_stride == 0: one horizon reference shared by the batch; otherwise ref_stride >= N*n_y.  Everything else is
+ * mpcq_mimo_step_device's.  Fr is never stored: it is block-Toeplitz, and with F[j] block row j of the operator
+ * block's row sums Frs (F[N] = 0) and ref_N = 0,
+ *   (Fr ref)_j = sum_{d=0}^{N-1-j} F[N-1-d] (ref_{j+d} - ref_{j+d+1}),
+ * accumulated in ascending d, then ascending y, in fp64 FMA.  A horizon-constant reference 1_N (x) yref leaves exact
+ * zeros and the last term F[j] yref, so it reproduces mpcq_mimo_step_device(yref) bit for bit.
+ * polish = 1 runs the polish pass of mpcq_mimo_step_polish_device afterwards (the same kernel, U_prev copy and
+ * mpcq_get_polish_info); polish = 0 is the plain step.
+ * ref_dev is read-only and must stay valid and unchanged until the step has finished on `stream`.  q is written
+ * eagerly: mpcq_device_view_get().q shows this step's q.
+ * Afterwards mpcq_mimo_sensitivity*, mpcq_mimo_step_vjp* and mpcq_mimo_step_gains* serve the step unchanged; their
+ * dyref is then the gradient with respect to a uniform shift of the reference (ref_b + 1_N (x) dy), and
+ * mpcq_mimo_step_ref_vjp_device gives the gradient with respect to ref_b itself.  mpcq_mimo_plant_vjp* would form gFr
+ * from a yref the step did not use: it returns MPCQ_ERR_ORDER until the next mpcq_mimo_step_device or
+ * mpcq_mimo_step_polish_device.
+ * MPCQ_ERR_ARG, nothing written: NULL X, U or ref; a non-zero ref_stride below N*n_y; polish not 0 or 1;
+ * settings.polish set; `stream` under graph capture when polish = 1.  MPCQ_ERR_ORDER as mpcq_mimo_step_device. */
+int mpcq_mimo_step_ref_device(mpcq_ctx *ctx, const double *X_dev, double *U_dev, const double *ref_dev,
+                              long long ref_stride, int polish, void *stream);
+/* Host-memory form (copies in/out, synchronises): X batch*n_x, U batch*n_u (updated), ref as above on the host. */
+int mpcq_mimo_step_ref(mpcq_ctx *ctx, const double *X, double *U, const double *ref, long long ref_stride, int polish);
 
 /* ---- active-set sensitivities of the last MIMO step --------------------------------
  * The definition of mpcq_sensitivity_device above, applied to the last mpcq_mimo_step_device of the context:
@@ -541,8 +565,10 @@ int mpcq_mimo_sensitivity(mpcq_ctx *ctx, const double *g, int n_rhs, double *gq,
  *   dX = Fx' gq + K' sum_{k < min(s_rows, N)} (gt_k - gb_k)   (batch*n_rhs*n_x)
  *   dU = Fu' gq + K0' sum_k (gb_k - gt_k)                     (batch*n_rhs*n_u)
  *   dyref = Frs' gq                                           (batch*n_rhs*n_y)
- * from the plant's own operator block, fp64 sums in ascending row index.  dyref is per QP: yref is one vector
- * for the whole batch, so a caller who wants its gradient sums dyref over the QPs.  Each output may be NULL, not
+ * from the plant's own operator block, fp64 sums in ascending row index.  dyref is per QP: mpcq_mimo_step_device's
+ * yref is one vector for the whole batch, so a caller who wants its gradient sums dyref over the QPs (after a
+ * mpcq_mimo_step_ref_device, dyref is the gradient with respect to a uniform shift of the QP's reference; the
+ * gradient with respect to the reference itself: mpcq_mimo_step_ref_vjp_device).  Each output may be NULL, not
  * all.  Otherwise as mpcq_mimo_sensitivity_device. */
 int mpcq_mimo_step_vjp_device(mpcq_ctx *ctx, const double *g_dev, int n_rhs, double *dX_dev, double *dU_dev,
                               double *dyref_dev, int *n_active_dev, void *stream);
@@ -551,6 +577,20 @@ int mpcq_mimo_step_vjp_device(mpcq_ctx *ctx, const double *g_dev, int n_rhs, dou
  * feedback gain.  (U_new = U + x*[0:n_u] adds the identity to dU.) */
 int mpcq_mimo_step_gains_device(mpcq_ctx *ctx, double *dX_dev, double *dU_dev, double *dyref_dev, int *n_active_dev,
                                 void *stream);
+/* mpcq_mimo_step_vjp_device with the gradient of the horizon reference in place of dyref:
+ *   dref = Fr' gq                                             (batch*n_rhs*N*n_y; block i, then y)
+ * from the row sums alone: with w_i = sum_{j<=i} F[N-1-i+j]' gq_j and w_{-1} = 0, dref_i = w_i - w_{i-1}, one thread
+ * per output, both sums in ascending j in fp64; sum_i dref_i = Frs' gq, which is dyref.  dX, dU and n_active are
+ * mpcq_mimo_step_vjp_device's bit for bit.  Refusals and ordering are those of mpcq_mimo_step_vjp_device; the
+ * last step may be a mpcq_mimo_step_device too (dref is then the gradient at ref = 1_N (x) yref).  No atomics: two
+ * calls give identical bits; a QP with n_active = -1 gets zeros. */
+int mpcq_mimo_step_ref_vjp_device(mpcq_ctx *ctx, const double *g_dev, int n_rhs, double *dX_dev, double *dU_dev,
+                                  double *dref_dev, int *n_active_dev, void *stream);
+/* Step gains with respect to the horizon reference: mpcq_mimo_step_ref_vjp_device with g = NULL and n_rhs = n_u. */
+int mpcq_mimo_step_ref_gains_device(mpcq_ctx *ctx, double *dX_dev, double *dU_dev, double *dref_dev, int *n_active_dev,
+                                    void *stream);
+/* Host-memory form (copies out, synchronises): dX batch*n_u*n_x, dU batch*n_u*n_u, dref batch*n_u*N*n_y, n_active. */
+int mpcq_mimo_step_ref_gains(mpcq_ctx *ctx, double *dX, double *dU, double *dref, int *n_active);
 
 /* ---- the last MIMO step differentiated in the plant model, the weights and the constraint data
  * The nine plant arrays are those mpcq_mimo_setup_plants_device read (device, fp64, plant-major; the caller vouches
@@ -572,7 +612,8 @@ int mpcq_mimo_step_gains_device(mpcq_ctx *ctx, double *dX_dev, double *dU_dev, d
  * the pull-back.  Read-only on the context, ordered after the context's last stream (an event) with the context's
  * next step ordered after it, as mpcq_mimo_sensitivity_device; after mpcq_mimo_step_polish_device the polished
  * iterate is read.  No atomics, sums in a fixed order: two calls give identical bits.
- * MPCQ_ERR_ORDER: no setup; no mpcq_mimo_step_device since the last MIMO setup.  MPCQ_ERR_ARG: a context whose last
+ * MPCQ_ERR_ORDER: no setup; no mpcq_mimo_step_device since the last MIMO setup; the last step was a
+ * mpcq_mimo_step_ref* (its horizon reference is not among the arguments).  MPCQ_ERR_ARG: a context whose last
  * setup is not a MIMO one; a NULL plant array, X or U_prev; every output NULL; `stream` under graph capture.  A
  * refused call writes nothing. */
 int mpcq_mimo_plant_vjp_device(mpcq_ctx *ctx, const double *g_dev, const double *Ad, const double *Bd, const double *Cd,

@@ -482,6 +482,65 @@ class BatchSolver:
                                                        C.c_void_p(yref_ptr or 0), C.c_void_p(stream or 0)),
                     "mpcq_mimo_step_polish_device")
 
+    # -- MIMO steps with a horizon reference per plant (mpcq_mimo_step_ref*)
+    def mimo_step_ref_device(self, X_ptr: int, U_ptr: int, ref_ptr: int, ref_stride: int, polish: bool = False,
+                             stream: int | None = None) -> None:
+        """``mimo_step_device`` with an output reference over the horizon per QP: ``ref_ptr`` holds N*ny doubles
+        (block i, then y) per QP, ``ref_stride`` doubles apart (0: one horizon reference for the batch), and must
+        stay valid until the step has finished.  ``polish``: ``mimo_step_polish_device``'s pass afterwards.
+        Asynchronous."""
+        self.solve_count += 1
+        _capi.check(lib().mpcq_mimo_step_ref_device(self._ctx, C.c_void_p(X_ptr), C.c_void_p(U_ptr),
+                                                    C.c_void_p(ref_ptr or 0), int(ref_stride), int(polish),
+                                                    C.c_void_p(stream or 0)), "mpcq_mimo_step_ref_device")
+
+    def _mimo_ref_len(self) -> int:
+        """N*ny, the doubles of one QP's horizon reference."""
+        nu, ny = getattr(self, "nu", 0), getattr(self, "ny", 0)
+        if not (nu and ny):
+            raise RuntimeError("the solver has no MIMO plants (BatchSolver.mimo_setup_plants_device)")
+        return self.n // nu * ny
+
+    def mimo_step_ref(self, X, U, ref, polish: bool = False) -> np.ndarray:
+        """Host arrays: X (batch, nx), U (batch, nu), ref (batch, N*ny), or (N*ny,) for one horizon reference shared
+        by the batch.  Returns the new U (batch, nu)."""
+        X, U, ref = _c64(X), _c64(U).copy(), _c64(ref)
+        nr = self._mimo_ref_len()
+        if X.shape != (self.batch, self.nx) or U.shape != (self.batch, self.nu) or \
+                ref.shape not in ((nr,), (self.batch, nr)):
+            raise ValueError(f"mimo_step_ref: X (batch, {self.nx}), U (batch, {self.nu}), ref (batch, {nr}) or ({nr},)")
+        self.solve_count += 1
+        _capi.check(lib().mpcq_mimo_step_ref(self._ctx, _dp(X), _dp(U), _dp(ref), nr if ref.ndim == 2 else 0,
+                                             int(polish)), "mpcq_mimo_step_ref")
+        return U
+
+    def mimo_step_ref_vjp_device(self, g_ptr: int = 0, n_rhs: int = 1, dX_ptr: int = 0, dU_ptr: int = 0,
+                                 dref_ptr: int = 0, n_active_ptr: int = 0, stream: int | None = None) -> None:
+        """``mimo_step_vjp_device`` with the gradient of the horizon reference, dref (batch, n_rhs, N*ny), in place
+        of dyref; asynchronous on ``stream``."""
+        ptrs = [C.c_void_p(p or 0) for p in (dX_ptr, dU_ptr, dref_ptr, n_active_ptr)]
+        _capi.check(lib().mpcq_mimo_step_ref_vjp_device(self._ctx, C.c_void_p(g_ptr or 0), int(n_rhs), *ptrs,
+                                                        C.c_void_p(stream or 0)), "mpcq_mimo_step_ref_vjp_device")
+
+    def mimo_step_ref_gains_device(self, dX_ptr: int = 0, dU_ptr: int = 0, dref_ptr: int = 0, n_active_ptr: int = 0,
+                                   stream: int | None = None) -> None:
+        """The gradients of the applied move x[0:n_u] with respect to X, the previous U and the horizon reference
+        (``mimo_step_ref_vjp_device`` with g = e_r, n_rhs = n_u) on device-resident buffers; asynchronous."""
+        ptrs = [C.c_void_p(p or 0) for p in (dX_ptr, dU_ptr, dref_ptr, n_active_ptr)]
+        _capi.check(lib().mpcq_mimo_step_ref_gains_device(self._ctx, *ptrs, C.c_void_p(stream or 0)),
+                    "mpcq_mimo_step_ref_gains_device")
+
+    def mimo_step_ref_gains(self):
+        """(dX, dU, dref, n_active) of the last MIMO step as numpy arrays: the gradient of component r of the applied
+        move with respect to X (batch, nu, nx), the previous U (batch, nu, nu) and the QP's horizon reference
+        (batch, nu, N*ny) at the current active set."""
+        nr = self._mimo_ref_len()
+        dX, dU = np.empty((self.batch, self.nu, self.nx)), np.empty((self.batch, self.nu, self.nu))
+        dref, na = np.empty((self.batch, self.nu, nr)), np.empty(self.batch, dtype=np.int32)
+        _capi.check(lib().mpcq_mimo_step_ref_gains(self._ctx, _dp(dX), _dp(dU), _dp(dref),
+                                                   na.ctypes.data_as(C.POINTER(C.c_int))), "mpcq_mimo_step_ref_gains")
+        return dX, dU, dref, na
+
     # -- active-set sensitivities of the last MIMO step (mpcq_mimo_sensitivity*, mpcq_mimo_step_*; DESIGN.md 4.15)
     def mimo_sensitivity(self, g=None, n_rhs: int | None = None):
         """(gq, gu, n_active) of the last ``mimo_step_device``: ``g`` of shape (batch, n_rhs, n) (or (batch, n) for one

@@ -27,6 +27,8 @@ EXPORTS = (
     "mpcq_sensitivity_data_device", "mpcq_sensitivity_data", "mpcq_condense_vjp_device", "mpcq_condense_vjp",
     "mpcq_mimo_sensitivity_device", "mpcq_mimo_sensitivity", "mpcq_mimo_step_vjp_device", "mpcq_mimo_step_gains_device",
     "mpcq_mimo_step_polish_device", "mpcq_mimo_plant_vjp_device", "mpcq_mimo_plant_vjp",
+    "mpcq_mimo_step_ref_device", "mpcq_mimo_step_ref", "mpcq_mimo_step_ref_vjp_device",
+    "mpcq_mimo_step_ref_gains_device", "mpcq_mimo_step_ref_gains",
 )
 # The symbols whose names follow OSQP's capitals (osqp_update_P_A).  They are kept apart from EXPORTS because the
 # header scan of tests/test_abi.py, which EXPORTS must equal, reads lower-case names only; lib() binds them with
@@ -113,6 +115,11 @@ def lib() -> C.CDLL:
         "mpcq_mimo_sensitivity": (C.c_int, [vp, dp, C.c_int, dp, dp, ip]),
         "mpcq_mimo_step_vjp_device": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
         "mpcq_mimo_step_gains_device": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+        "mpcq_mimo_step_ref_device": (C.c_int, [vp, vp, vp, vp, C.c_longlong, C.c_int, vp]),
+        "mpcq_mimo_step_ref": (C.c_int, [vp, dp, dp, dp, C.c_longlong, C.c_int]),
+        "mpcq_mimo_step_ref_vjp_device": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp]),
+        "mpcq_mimo_step_ref_gains_device": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+        "mpcq_mimo_step_ref_gains": (C.c_int, [vp, dp, dp, dp, ip]),
         "mpcq_mimo_plant_vjp_device": (C.c_int, [vp, vp] + [vp] * 9 + [vp] * 3 + [vp] * 9 + [vp, vp]),
         "mpcq_mimo_plant_vjp": (C.c_int, [vp, dp] + [dp] * 9 + [dp] * 3 + [dp] * 9 + [ip]),
         "mpcq_get_path": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -201,6 +201,7 @@ struct mpcq_ctx {
     int mimo_N = 0, mimo_nx = 0, mimo_nu = 0, mimo_ny = 0, mimo_srows = 0, mimo_diag_k0 = 0;
     bool mimo_only = false;  // n > 32 or m > 64 per plant: only the MIMO entry points serve it
     bool mimo_stepped = false;  // a mpcq_mimo_step_device since the last MIMO setup (mpcq_mimo_sensitivity* needs one)
+    bool mimo_ref_step = false; // that step was a mpcq_mimo_step_ref* (mpcq_mimo_plant_vjp* knows yref only: refused)
     // mpcq_mimo_plant_vjp*: mimo_sens_kernel's (gq, gu, n_active) for the call's g, which mimo_plant_vjp_kernel reads
     // (batch*n, batch*2n doubles, then batch ints; allocated on first use)
     DevBuf<double> d_mimo_pv;

@@ -364,6 +364,7 @@ int mpcq_mimo_setup_plants_device(mpcq_ctx *c, int nx, int nu, int ny, int s_row
     c->mode = mpcq_ctx::Mode::None;
     c->sens_ok = false;
     c->mimo_stepped = false;
+    c->mimo_ref_step = false;
     c->pol_valid = false;
     c->gen++;
     hipStream_t s = (hipStream_t)stream;
@@ -407,14 +408,40 @@ int mpcq_mimo_setup_plants_device(mpcq_ctx *c, int nx, int nu, int ny, int s_row
     return MPCQ_OK;
 }
 
-int mpcq_mimo_step_device(mpcq_ctx *c, const double *X, double *U, const double *yref, void *stream)
+}  // extern "C"
+
+namespace {
+
+// The reference of one MIMO step: yref (n_y values for the whole batch, held over the horizon; NULL: 0) of
+// mpcq_mimo_step_device, or with `horizon` a horizon of N*n_y values per QP, `stride` doubles apart (0: one for the
+// batch), of mpcq_mimo_step_ref_device
+struct MimoRef {
+    const double *yref = nullptr, *ref = nullptr;
+    long long stride = 0;
+    bool horizon = false;
+};
+
+// The refusals of a MIMO step, in the order of include/mpcq.h, before anything is enqueued or written
+int mimo_step_check(mpcq_ctx *c, const char *fn, const double *X, const double *U, const MimoRef &r, bool polish,
+                    hipStream_t s)
 {
     int rc = check_ctx(c, kNone);
     if (rc) return rc;
-    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal("mpcq_mimo_step_device"));
-    if ((rc = materialize_xy(c))) return rc;  // (a pending lazy x, y first: the kernel below rewrites the state)
+    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal(fn));
     if (c->mode != mpcq_ctx::Mode::Mimo) return fail(MPCQ_ERR_ORDER, "mpcq_mimo_setup_plants_device has not succeeded");
     if (!X || !U) return fail(MPCQ_ERR_ARG, "null X/U");
+    if (r.horizon) {
+        if (!r.ref) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null ref");
+        if (r.stride != 0 && r.stride < (long long)c->mimo_N * c->mimo_ny)
+            return fail(MPCQ_ERR_ARG, std::string(fn) + ": ref_stride is 0 (one reference for the batch) or >= N*n_y");
+    }
+    return polish ? refuse_capture(fn, s) : MPCQ_OK;
+}
+
+int mimo_step_enqueue(mpcq_ctx *c, const double *X, double *U, const MimoRef &r, void *stream)
+{
+    int rc = materialize_xy(c);  // (a pending lazy x, y first: the kernel below rewrites the state)
+    if (rc) return rc;
     mpcq::MimoArgs a{};
     a.batch = c->dims.batch;
     a.N = c->mimo_N; a.nx = c->mimo_nx; a.nu = c->mimo_nu; a.ny = c->mimo_ny; a.s_rows = c->mimo_srows;
@@ -424,7 +451,7 @@ int mpcq_mimo_step_device(mpcq_ctx *c, const double *X, double *U, const double 
     a.st = to_solver(c->set);
     const int ct = c->set.check_termination;
     a.adaptive_interval = c->set.adaptive_rho_interval ? c->set.adaptive_rho_interval : (ct ? 4 * ct : 100);
-    a.X = X; a.U = U; a.yref = yref;
+    a.X = X; a.U = U; a.yref = r.horizon ? nullptr : r.yref;
     a.q_out = c->d_q; a.u_out = c->d_u;
     a.xs = (double *)c->d_xs; a.zs = (double *)c->d_zs; a.ys = (double *)c->d_ys; a.rhos = (double *)c->d_rhos;
     a.warm = c->set.warm_start;
@@ -436,7 +463,8 @@ int mpcq_mimo_step_device(mpcq_ctx *c, const double *X, double *U, const double 
         a.stamps = c->d_stamps;
     }
     hipStream_t s = (hipStream_t)stream;
-    const int lr = mpcq_internal_mimo_solve_launch(&a, s);
+    const int lr = r.horizon ? mpcq_internal_mimo_solve_ref_launch(&a, r.ref, r.stride, s)
+                             : mpcq_internal_mimo_solve_launch(&a, s);
     if (lr) return fail(lr == -1 ? MPCQ_ERR_ARG : MPCQ_ERR_HIP, "mimo solve launch failed");
     if (stp && *stp) {
         std::vector<long long> h(8 * (size_t)a.batch);
@@ -450,26 +478,22 @@ int mpcq_mimo_step_device(mpcq_ctx *c, const double *X, double *U, const double 
     c->last = s;
     c->fresh = false;
     c->mimo_stepped = true;
+    c->mimo_ref_step = r.horizon;
     c->pol_valid = false;
     return MPCQ_OK;
 }
 
-int mpcq_mimo_step_polish_device(mpcq_ctx *c, const double *X, double *U, const double *yref, void *stream)
+// The step, then OSQP's polish of every SOLVED QP on the same stream (mpcq_mimo_polish.hip)
+int mimo_step_polish_enqueue(mpcq_ctx *c, const double *X, double *U, const MimoRef &r, void *stream)
 {
-    const char *fn = "mpcq_mimo_step_polish_device";
-    int rc = check_ctx(c, kNone);
-    if (rc) return rc;
-    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal(fn));
-    if (c->mode != mpcq_ctx::Mode::Mimo) return fail(MPCQ_ERR_ORDER, "mpcq_mimo_setup_plants_device has not succeeded");
-    if (!X || !U) return fail(MPCQ_ERR_ARG, "null X/U");
+    int rc = MPCQ_OK;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = refuse_capture(fn, s))) return rc;
     const size_t B = c->dims.batch, nu = c->mimo_nu;
     if ((rc = c->d_pol_status.alloc(4 * B)) || (rc = c->d_pol_nact.alloc(4 * B)) || (rc = c->d_pol_res.alloc(8 * 2 * B)) ||
         (rc = c->d_mimo_Uprev.grow(8 * B * nu, s, "mimo polish staging")))
         return rc;
     HIPCHK(hipMemcpyAsync(c->d_mimo_Uprev, U, 8 * B * nu, hipMemcpyDeviceToDevice, s));
-    if ((rc = mpcq_mimo_step_device(c, X, U, yref, stream))) return rc;
+    if ((rc = mimo_step_enqueue(c, X, U, r, stream))) return rc;
     mpcq::MimoPolishArgs a{};
     a.batch = c->dims.batch;
     a.N = c->mimo_N; a.nx = c->mimo_nx; a.nu = c->mimo_nu; a.ny = c->mimo_ny;
@@ -490,6 +514,72 @@ int mpcq_mimo_step_polish_device(mpcq_ctx *c, const double *X, double *U, const 
     if (lr) return fail(MPCQ_ERR_HIP, std::string("mimo polish kernel launch failed: ") + hipGetErrorString(err));
     c->pol_valid = true;
     return MPCQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpcq_mimo_step_device(mpcq_ctx *c, const double *X, double *U, const double *yref, void *stream)
+{
+    MimoRef r;
+    r.yref = yref;
+    int rc = mimo_step_check(c, "mpcq_mimo_step_device", X, U, r, false, (hipStream_t)stream);
+    if (rc) return rc;
+    return mimo_step_enqueue(c, X, U, r, stream);
+}
+
+int mpcq_mimo_step_polish_device(mpcq_ctx *c, const double *X, double *U, const double *yref, void *stream)
+{
+    MimoRef r;
+    r.yref = yref;
+    int rc = mimo_step_check(c, "mpcq_mimo_step_polish_device", X, U, r, true, (hipStream_t)stream);
+    if (rc) return rc;
+    return mimo_step_polish_enqueue(c, X, U, r, stream);
+}
+
+int mpcq_mimo_step_ref_device(mpcq_ctx *c, const double *X, double *U, const double *ref, long long ref_stride,
+                              int polish, void *stream)
+{
+    const char *fn = "mpcq_mimo_step_ref_device";
+    if (polish != 0 && polish != 1) return fail(MPCQ_ERR_ARG, std::string(fn) + ": polish is 0 or 1");
+    MimoRef r;
+    r.ref = ref; r.stride = ref_stride; r.horizon = true;
+    int rc = mimo_step_check(c, fn, X, U, r, polish == 1, (hipStream_t)stream);
+    if (rc) return rc;
+    return polish ? mimo_step_polish_enqueue(c, X, U, r, stream) : mimo_step_enqueue(c, X, U, r, stream);
+}
+
+int mpcq_mimo_step_ref(mpcq_ctx *c, const double *X, double *U, const double *ref, long long ref_stride, int polish)
+{
+    const char *fn = "mpcq_mimo_step_ref";
+    if (polish != 0 && polish != 1) return fail(MPCQ_ERR_ARG, std::string(fn) + ": polish is 0 or 1");
+    MimoRef r;
+    r.ref = ref; r.stride = ref_stride; r.horizon = true;
+    int rc = mimo_step_check(c, fn, X, U, r, polish == 1, c ? c->last : nullptr);
+    if (rc) return rc;
+    const size_t B = c->dims.batch, nx = c->mimo_nx, nu = c->mimo_nu, nr = (size_t)c->mimo_N * c->mimo_ny;
+    const size_t rows = ref_stride ? B : 1;
+    // staging of this call alone: X, U, then the references packed (B rows of N*n_y, or the one shared row)
+    DevBuf<double> d;
+    if ((rc = d.alloc(8 * (B * (nx + nu) + rows * nr), "mimo reference staging"))) return rc;
+    struct Drain {  // (the stream is waited for, whatever the outcome, before the staging goes away)
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{c->last};
+    double *dX = d, *dU = dX + B * nx, *dr = dU + B * nu;
+    if ((rc = h2d(dX, X, 8 * B * nx, c->last)) || (rc = h2d(dU, U, 8 * B * nu, c->last))) return rc;
+    if (rows == 1 || ref_stride == (long long)nr) {
+        if ((rc = h2d(dr, ref, 8 * rows * nr, c->last))) return rc;
+    } else {
+        HIPCHK(hipMemcpy2DAsync(dr, 8 * nr, ref, 8 * (size_t)ref_stride, 8 * nr, rows, hipMemcpyHostToDevice, c->last));
+        HIPCHK(hipStreamSynchronize(c->last));
+    }
+    r.ref = dr;
+    r.stride = ref_stride ? (long long)nr : 0;
+    if ((rc = polish ? mimo_step_polish_enqueue(c, dX, dU, r, c->last) : mimo_step_enqueue(c, dX, dU, r, c->last)))
+        return rc;
+    return d2h(c, U, dU, 8 * B * nu);
 }
 
 }  // extern "C"

@@ -114,8 +114,9 @@ int mimo_sens_check(mpcq_ctx *c, const char *fn, bool implicit_g, int n_rhs, boo
 }
 
 // The kernel on s, ordered after the context's last stream; the context's next launches ordered after it.
+// dref (batch * n_rhs * N n_y, or null): the chain rule on a horizon reference, Fr' gq.
 int mimo_sens_enqueue(mpcq_ctx *c, const double *g, int n_rhs, double *gq, double *gu, double *dX, double *dU,
-                      double *dyref, int *nact, hipStream_t s)
+                      double *dyref, int *nact, hipStream_t s, double *dref = nullptr)
 {
     if (int rc = order_after_last(c, s)) return rc;
     mpcq::MimoSensArgs a{};
@@ -130,7 +131,7 @@ int mimo_sens_enqueue(mpcq_ctx *c, const double *g, int n_rhs, double *gq, doubl
     a.status = c->d_status;
     a.g = g;
     a.gq = gq; a.gu = gu;
-    a.dX = dX; a.dU = dU; a.dyref = dyref;
+    a.dX = dX; a.dU = dU; a.dyref = dyref; a.dref = dref;
     a.n_active = nact;
     a.delta = c->set.delta;
     a.refine = c->set.polish_refine_iter;
@@ -167,6 +168,9 @@ int mimo_plant_vjp_check(mpcq_ctx *c, const char *fn, const MimoPlantPtrs &p, co
         return fail(MPCQ_ERR_ARG, std::string(fn) + ": the context was not set up by mpcq_mimo_setup_plants_device");
     if (!c->mimo_stepped)
         return fail(MPCQ_ERR_ORDER, std::string(fn) + ": needs a mpcq_mimo_step_device since the last setup");
+    if (c->mimo_ref_step)  // (gFr would be formed from a yref the step did not use)
+        return fail(MPCQ_ERR_ORDER, std::string(fn) + ": the last step was a mpcq_mimo_step_ref*, whose horizon "
+                                                      "reference this call does not know; needs a mpcq_mimo_step_device");
     bool any_out = n_active != nullptr;
     for (int k = 0; k < 9; k++) {
         if (!p.in[k]) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null plant array");
@@ -354,6 +358,45 @@ int mpcq_mimo_step_gains_device(mpcq_ctx *c, double *dX, double *dU, double *dyr
                              dX || dU || dyref || n_active, (hipStream_t)stream);
     if (rc) return rc;
     return mimo_sens_enqueue(c, nullptr, c->mimo_nu, nullptr, nullptr, dX, dU, dyref, n_active, (hipStream_t)stream);
+}
+
+int mpcq_mimo_step_ref_vjp_device(mpcq_ctx *c, const double *g, int n_rhs, double *dX, double *dU, double *dref,
+                                  int *n_active, void *stream)
+{
+    int rc = mimo_sens_check(c, "mpcq_mimo_step_ref_vjp_device", !g, n_rhs, dX || dU || dref || n_active,
+                             (hipStream_t)stream);
+    if (rc) return rc;
+    return mimo_sens_enqueue(c, g, n_rhs, nullptr, nullptr, dX, dU, nullptr, n_active, (hipStream_t)stream, dref);
+}
+
+int mpcq_mimo_step_ref_gains_device(mpcq_ctx *c, double *dX, double *dU, double *dref, int *n_active, void *stream)
+{
+    int rc = mimo_sens_check(c, "mpcq_mimo_step_ref_gains_device", true, c ? std::max(c->mimo_nu, 1) : 1,
+                             dX || dU || dref || n_active, (hipStream_t)stream);
+    if (rc) return rc;
+    return mimo_sens_enqueue(c, nullptr, c->mimo_nu, nullptr, nullptr, dX, dU, nullptr, n_active, (hipStream_t)stream, dref);
+}
+
+int mpcq_mimo_step_ref_gains(mpcq_ctx *c, double *dX, double *dU, double *dref, int *n_active)
+{
+    int rc = mimo_sens_check(c, "mpcq_mimo_step_ref_gains", true, c ? std::max(c->mimo_nu, 1) : 1,
+                             dX || dU || dref || n_active, c ? c->last : nullptr);
+    if (rc) return rc;
+    const size_t B = c->dims.batch, nx = c->mimo_nx, R = c->mimo_nu, nr = (size_t)c->mimo_N * c->mimo_ny;
+    // staging of this call alone: dX, dU, dref of the n_u right-hand sides, then B ints
+    DevBuf<double> d;
+    if ((rc = d.alloc(8 * (B * R * (nx + R + nr) + (B + 1) / 2), "mimo step-gain staging"))) return rc;
+    struct Drain {  // (the stream is waited for, whatever the outcome, before the staging goes away)
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{c->last};
+    double *ddX = d, *ddU = ddX + B * R * nx, *ddr = ddU + B * R * R;
+    int *dna = (int *)(ddr + B * R * nr);
+    if ((rc = mimo_sens_enqueue(c, nullptr, (int)R, nullptr, nullptr, ddX, ddU, nullptr, dna, c->last, ddr))) return rc;
+    if ((rc = d2h(c, dX, ddX, 8 * B * R * nx)) || (rc = d2h(c, dU, ddU, 8 * B * R * R)) ||
+        (rc = d2h(c, dref, ddr, 8 * B * R * nr)))
+        return rc;
+    return d2h(c, n_active, dna, 4 * B);
 }
 
 int mpcq_mimo_plant_vjp_device(mpcq_ctx *c, const double *g, const double *Ad, const double *Bd, const double *Cd,

@@ -437,6 +437,7 @@ struct MimoSensArgs {
     int *n_active;              // [batch] rows of the reduced system, -1 where no sensitivity exists (or null)
     double delta;
     int refine;
+    double *dref;               // [batch][n_rhs] N*ny: Fr' gq, the chain rule on a horizon reference (or null)
 };
 
 // Arguments of polish_mimo_kernel (mpcq_mimo_polish.hip): OSQP's polish of the MIMO step just enqueued, one workgroup
@@ -781,6 +782,9 @@ int mpcq_internal_order_info(int batch, const int *list, const int *slot, int *s
 // (one 512-thread workgroup per QP: KKT inverse by Gauss-Jordan in VGPRs, structured A).
 int mpcq_internal_mimo_setup_launch(const mpcq::MimoSetupArgs *a, hipStream_t s);
 int mpcq_internal_mimo_solve_launch(const mpcq::MimoArgs *a, hipStream_t s);
+// The same step with a horizon reference per QP in place of a->yref (mimo_solve_ref_kernel): ref +
+// b ref_stride holds N*ny values, ref_stride 0 one horizon for the batch.  Same return codes.
+int mpcq_internal_mimo_solve_ref_launch(const mpcq::MimoArgs *a, const double *ref, long long ref_stride, hipStream_t s);
 // Sensitivities of the last MIMO step with the chain rule as the kernel's tail (mpcq_mimo_sens.hip; every shape
 // the MIMO setup accepts): 0 launched, -1 unsupported shape or n_rhs, -2 HIP error (*err).  The workgroup's
 // dynamic LDS bytes for n variables: mpcq_internal_mimo_sens_lds.

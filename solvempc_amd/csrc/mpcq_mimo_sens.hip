@@ -13,6 +13,8 @@
 //
 // The chain rule of the step gains (q = Fx X + Fu U + Frs yref, u = W0 + Sbar X + Ku U) is the kernel's tail: gq
 // and gu of a right-hand side are still in LDS, one thread per output element, sums in ascending row index.
+// With a horizon reference per QP (mpcq_mimo_step_ref_vjp_device) the tail also forms dref = Fr' gq
+// from Frs alone, one thread per output.
 // No atomics anywhere: two calls give identical bits.  Nothing of the context is written.
 #include "mpcq_internal.h"
 #include "mpcq_wgkkt.h"
@@ -187,6 +189,19 @@ __global__ __launch_bounds__(kMsThreads) void mimo_sens_kernel(MimoSensArgs a)
                     }
                 }
             }
+            // dref = Fr' gq from the row sums alone (F[j]: block row j of Frs): one thread per
+            // (i, y), w_i = sum_{j<=i} F[N-1-i+j]' gq_j and w_{i-1} in ascending j, then their difference
+            if (a.dref)
+                for (int o = t; o < N * ny; o += kMsThreads) {
+                    const int i = o / ny, y = o - i * ny;
+                    const double *F = ops + L.Frs + y;
+                    double w1 = 0.0, w0 = 0.0;
+                    for (int j = 0; j <= i; j++)
+                        for (int c = 0; c < NU; c++) w1 += F[((N - 1 - i + j) * NU + c) * ny] * gqv[j * NU + c];
+                    for (int j = 0; j < i; j++)
+                        for (int c = 0; c < NU; c++) w0 += F[((N - i + j) * NU + c) * ny] * gqv[j * NU + c];
+                    a.dref[(br * N + i) * ny + y] = w1 - w0;
+                }
             __syncthreads();  // (gqv, guv are the next right-hand side's scratch)
         }
         if (t == 0 && a.n_active) a.n_active[b] = ok ? mr : -1;

@@ -171,6 +171,43 @@ class _MimoSolution(torch.autograd.Function):
         return None, None, dX, dU, dy.sum(dim=0)  # (yref is one vector for the whole batch)
 
 
+class _MimoRefSolution(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, polish, X, U, ref):
+        B, n = solver.batch, solver.n
+        nx, nu, ny = solver.nx, getattr(solver, "nu", 0), getattr(solver, "ny", 0)
+        if not (nu and ny):
+            raise RuntimeError("mimo_ref_solution: the solver has no MIMO plants (BatchSolver.mimo_setup_plants_device)")
+        nr = n // nu * ny
+        for name, t, shape in (("X", X, (B, nx)), ("U", U, (B, nu)), ("ref", ref, (B, nr))):
+            if not (t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == shape):
+                raise ValueError(f"mimo_ref_solution: {name} must be a device fp64 tensor of shape {shape}")
+        Xc, Uc, rc = X.detach().contiguous(), U.detach().clone().contiguous(), ref.detach().contiguous()
+        stream = torch.cuda.current_stream(X.device).cuda_stream
+        solver.mimo_step_ref_device(Xc.data_ptr(), Uc.data_ptr(), rc.data_ptr(), nr, polish, stream)
+        view = solver.device_view()
+        x = torch.as_tensor(_DevArray(view["x"], (B, n), "<f8"), device=X.device).clone()
+        status = torch.as_tensor(_DevArray(view["status"], (B,), "<i4"), device=X.device).clone()
+        ctx.keep = (Xc, Uc, rc)  # (rc stays alive until the step has finished)
+        ctx.solver, ctx.count, ctx.dims = solver, solver.solve_count, (nx, nu, nr)
+        ctx.mark_non_differentiable(status)
+        return x, status
+
+    @staticmethod
+    def backward(ctx, gx, _gstatus):
+        solver = ctx.solver
+        if solver.solve_count != ctx.count:
+            raise RuntimeError("mimo_ref_solution.backward: the solver has solved again since this forward pass, so "
+                               "its state is no longer this solve's; run backward before the next solve")
+        B, (nx, nu, nr) = solver.batch, ctx.dims
+        g = gx.contiguous()
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=g.device)
+        dX, dU, dref = new(B, nx), new(B, nu), new(B, nr)
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        solver.mimo_step_ref_vjp_device(g.data_ptr(), 1, dX.data_ptr(), dU.data_ptr(), dref.data_ptr(), 0, stream)
+        return None, None, dX, dU, dref
+
+
 _MIMO_PLANT = ("Ad", "Bd", "Cd", "Q", "R", "RD", "K", "K0", "w0")
 
 
@@ -342,6 +379,16 @@ def mimo_solution(solver, X, U, yref, polish=False):
     unchanged backward pass then reads the polished iterate.  ``backward`` must run before the solver solves
     again."""
     return _MimoSolution.apply(solver, bool(polish), X, U, yref)
+
+
+def mimo_ref_solution(solver, X, U, ref, polish=False):
+    """``mimo_solution`` with an output reference over the horizon per QP (trajectory tracking with preview):
+    ``solver.mimo_step_ref_device`` on device fp64 tensors X (batch, nx), U (batch, nu), ref (batch, N*ny; block i of
+    the horizon, then y), differentiable with respect to all three.  Returns ``(x, status)``; the caller's U is left
+    alone.  Backward is one ``BatchSolver.mimo_step_ref_vjp_device`` call on the incoming cotangent:
+    every QP's own gradient of its reference, nothing summed over the batch, zero for a QP that did not end SOLVED.
+    ``polish`` as in ``mimo_solution``.  ``backward`` must run before the solver solves again."""
+    return _MimoRefSolution.apply(solver, bool(polish), X, U, ref)
 
 
 def mimo_plant_solution(solver, Ad, Bd, Cd, Q, R, RD, K, K0, w0, X, U, yref, s_rows, polish=False, setup=True):
