@@ -404,7 +404,8 @@ typedef struct mpcq_stream_log {
  * run's `stream` and must stay valid until that stream has finished.
  * MPCQ_ERR_ARG: a pointer is set and rows < 1 or step0 < 0.  A run returns MPCQ_ERR_ARG, before anything is
  * enqueued (X_dev, U_dev, the counters and the buffers untouched), when any of its rows would fall outside
- * [0, rows).  Not served: MIMO (no stream) and mpcq_mpc_plants_step_device. */
+ * [0, rows).  Not served: mpcq_mpc_plants_step_device; a MIMO run takes a record of its own as an argument
+ * (mpcq_mimo_log, mpcq_mimo_run_device). */
 int mpcq_mpc_set_stream_log(mpcq_ctx *ctx, const mpcq_stream_log *log);
 
 /* Condensed-QP construction on device `device` for n_plants SISO plants (ModelPredictiveControlAPI
@@ -536,6 +537,74 @@ int mpcq_mimo_step_ref_device(mpcq_ctx *ctx, const double *X_dev, double *U_dev,
                               long long ref_stride, int polish, void *stream);
 /* Host-memory form (copies in/out, synchronises): X batch*n_x, U batch*n_u (updated), ref as above on the host. */
 int mpcq_mimo_step_ref(mpcq_ctx *ctx, const double *X, double *U, const double *ref, long long ref_stride, int polish);
+
+/* ---- closed-loop MIMO runs: simulated plant, reference schedule, record ------------
+ * The MIMO twins of mpcq_mpc_set_plant / mpcq_mpc_simulate_device / mpcq_mpc_run_device / mpcq_mpc_run_ref_device /
+ * mpcq_mpc_set_stream_log.  The control step stays the kernels of mpcq_mimo_step*_device, launched once per step;
+ * between two steps one kernel advances every plant, writes the record row and adds to the totals.  No hipGraph.
+ *
+ * The simulated plant of every QP: Ad_dev batch*n_x*n_x, Bd_dev batch*n_x*n_u (device, fp64, QP-major, row-major
+ * blocks), copied device-to-device on `stream` into buffers the context owns; n_x, n_u are the context's own from
+ * mpcq_mimo_setup_plants_device.  It need not be the model the controller was set up with.  A later MIMO setup keeps
+ * the plant when n_x and n_u are unchanged and drops it otherwise.  A run on another stream is ordered after the
+ * copy by the caller.  MPCQ_ERR_ORDER: no MIMO setup.  MPCQ_ERR_ARG: NULL Ad / Bd, `stream` under graph capture. */
+int mpcq_mimo_set_plant_device(mpcq_ctx *ctx, const double *Ad_dev, const double *Bd_dev, void *stream);
+/* One plant update in place on device-resident X (batch*n_x) from U (batch*n_u):  X_b <- Ad_b X_b + Bd_b U_b + w.
+ * Row i is sum_t Ad[i,t] x_t in ascending t, then sum_j Bd[i,j] u_j in ascending j, then + w_i, in fp64, every
+ * product rounded before it is added (no FMA).  w of QP b is the counter-based noise of mpcq_mpc_simulate_device
+ * keyed by (seed, first_qp + b, step): Box-Muller pairs from draws step*64 + 2p, 2p + 1, ceil(n_x/2) <= 6 pairs,
+ * component i < ceil(n_x/2) the cosine of pair i, the others the sine of pair i - ceil(n_x/2)
+ * (workload.plant_noise); noise_std == 0 draws nothing.  Asynchronous on `stream`.
+ * MPCQ_ERR_ORDER: no MIMO setup, or no plant.  MPCQ_ERR_ARG: NULL X / U, step < 0. */
+int mpcq_mimo_simulate_device(mpcq_ctx *ctx, double *X_dev, const double *U_dev, unsigned long long seed,
+                              long long first_qp, long long step, double noise_std, void *stream);
+
+/* Record of a run.  Caller-owned device pointers, any of which may be NULL (not recorded).  The four per-step arrays
+ * are step-major as mpcq_stream_log's; row r = s - step0 of control step s holds
+ *   U      [(r*batch + b)*n_u + j]  U_b after the step's control step (the row before, or the call's input for row
+ *                                   0 of the first call, where the step did not end MPCQ_SOLVED)
+ *   X      [(r*batch + b)*n_x + i]  X_b after the step's plant update
+ *   status [r*batch + b], iter [r*batch + b]   those of the step's solve
+ * and the two totals are batch ints each: the ADMM iterations of the call's steps and the number of them that did
+ * not end MPCQ_SOLVED.  A run with steps > 0 zeroes the totals when it starts and accumulates them on the device
+ * (each QP is owned by one 16-lane group: no atomics).  rows and step0 are read when one of the four is set. */
+typedef struct mpcq_mimo_log {
+    double *U, *X;
+    int *status, *iter;
+    int *iters_total, *unsolved_total;
+    long long rows;   /* capacity in control steps */
+    long long step0;  /* absolute control step stored in row 0 */
+} mpcq_mimo_log;
+
+/* `steps` rounds of [control step; plant update] for the absolute control steps first_step .. first_step+steps-1;
+ * X_dev / U_dev evolve in place.  The control step is mpcq_mimo_step_device(yref_dev), or with polish = 1
+ * mpcq_mimo_step_polish_device(yref_dev); the plant update of step s is mpcq_mimo_simulate_device(step = s).
+ * A run is, bit for bit, that sequence of single calls: X, U, the context's x, y, status, iter, rho, q, warm state
+ * and polish info are the last step's, every log row is what the single calls would have shown after the step, and
+ * the context is left as the sequence leaves it, so mpcq_mimo_sensitivity*, mpcq_mimo_step_vjp* and
+ * mpcq_mimo_step_*gains* serve the run's last control step unchanged.  `log` may be NULL.  steps == 0 enqueues and
+ * writes nothing and returns MPCQ_OK.  Asynchronous on `stream`; yref_dev and the log's buffers must stay valid
+ * until it has finished.
+ * Refused before anything is enqueued or written.  MPCQ_ERR_ORDER: no MIMO setup, or no plant.  MPCQ_ERR_ARG: NULL
+ * X / U; steps < 0; first_step < 0; polish not 0 or 1; settings.polish set; one of the log's four per-step pointers
+ * set with rows < 1, step0 < 0 or a row of the call outside [0, rows); `stream` under graph capture. */
+int mpcq_mimo_run_device(mpcq_ctx *ctx, double *X_dev, double *U_dev, const double *yref_dev, int steps,
+                         unsigned long long seed, long long first_qp, long long first_step, double noise_std,
+                         int polish, const mpcq_mimo_log *log, void *stream);
+/* The same run with a reference schedule of sched_len blocks of n_y values per QP, sched_stride doubles apart
+ * (0: one schedule for the batch; otherwise >= sched_len*n_y).  Control step s is
+ * mpcq_mimo_step_ref_device(ref, ref_stride, polish) on the window
+ *   ref_b[i*n_y + y] = sched_dev[b*sched_stride + min(s + i, sched_len - 1)*n_y + y],  i < N
+ * (the last block is held, as in mpcq_mpc_run_ref_device).  While s + N <= sched_len the step reads the schedule in
+ * place (ref = sched_dev + s*n_y); a call that goes further first copies, once, 2N-1 blocks per schedule row from
+ * block max(sched_len - N, 0) with the last block repeated into staging the context owns (8 (2N-1) n_y bytes per QP,
+ * 5.7 KB at n_y 12, N 30; one row for a shared schedule; allocated by the first such call) and its later steps read
+ * their windows there.  sched_dev must stay valid and unchanged until `stream` has finished.
+ * Also MPCQ_ERR_ARG: NULL schedule, sched_len < 1, a non-zero sched_stride below sched_len*n_y. */
+int mpcq_mimo_run_ref_device(mpcq_ctx *ctx, double *X_dev, double *U_dev, const double *sched_dev, int sched_len,
+                             long long sched_stride, int steps, unsigned long long seed, long long first_qp,
+                             long long first_step, double noise_std, int polish, const mpcq_mimo_log *log,
+                             void *stream);
 
 /* ---- active-set sensitivities of the last MIMO step --------------------------------
  * The definition of mpcq_sensitivity_device above, applied to the last mpcq_mimo_step_device of the context:

@@ -541,6 +541,105 @@ class BatchSolver:
                                                    na.ctypes.data_as(C.POINTER(C.c_int))), "mpcq_mimo_step_ref_gains")
         return dX, dU, dref, na
 
+    # -- closed-loop MIMO runs: simulated plant, reference schedule, record (mpcq_mimo_run*)
+    def mimo_set_plant_device(self, Ad_ptr: int, Bd_ptr: int, stream: int | None = None) -> None:
+        """The simulated plant of every QP, copied device-to-device from Ad (batch, nx, nx) and Bd (batch, nx, nu);
+        it need not be the model the controller was set up with."""
+        _capi.check(lib().mpcq_mimo_set_plant_device(self._ctx, C.c_void_p(Ad_ptr or 0), C.c_void_p(Bd_ptr or 0),
+                                                     C.c_void_p(stream or 0)), "mpcq_mimo_set_plant_device")
+
+    def mimo_simulate_device(self, X_ptr: int, U_ptr: int, seed: int, first_qp: int, step: int, noise_std: float,
+                             stream: int | None = None) -> None:
+        """One plant update in place, X_b <- Ad_b X_b + Bd_b U_b + workload.plant_noise(seed, first_qp + b, 1, step,
+        nx, noise_std); asynchronous."""
+        _capi.check(lib().mpcq_mimo_simulate_device(self._ctx, C.c_void_p(X_ptr or 0), C.c_void_p(U_ptr or 0), seed,
+                                                    first_qp, step, float(noise_std), C.c_void_p(stream or 0)),
+                    "mpcq_mimo_simulate_device")
+
+    @staticmethod
+    def mimo_log(U_ptr: int = 0, X_ptr: int = 0, status_ptr: int = 0, iter_ptr: int = 0, iters_total_ptr: int = 0,
+                 unsolved_total_ptr: int = 0, rows: int = 0, step0: int = 0) -> _capi.MimoLog:
+        """The record argument of ``mimo_run_device`` / ``mimo_run_ref_device`` (mpcq_mimo_log): device buffers,
+        step-major U (rows, batch, nu) and X (rows, batch, nx) fp64, status and iter (rows, batch) int32, the totals
+        (batch,) int32; any may be 0.  Control step ``step0 + r`` fills row r."""
+        return _capi.MimoLog(U_ptr or None, X_ptr or None, status_ptr or None, iter_ptr or None,
+                             iters_total_ptr or None, unsolved_total_ptr or None, int(rows), int(step0))
+
+    def mimo_run_device(self, X_ptr: int, U_ptr: int, yref_ptr: int, steps: int, seed: int, first_qp: int,
+                        first_step: int, noise_std: float, polish: bool = False, log: _capi.MimoLog | None = None,
+                        stream: int | None = None) -> None:
+        """``steps`` rounds of [``mimo_step_device`` (``polish``: ``mimo_step_polish_device``); ``mimo_simulate_device``]
+        for the control steps first_step .. first_step+steps-1, bit for bit those calls; X, U evolve in place.
+        Asynchronous."""
+        self.solve_count += 1
+        _capi.check(lib().mpcq_mimo_run_device(self._ctx, C.c_void_p(X_ptr or 0), C.c_void_p(U_ptr or 0),
+                                               C.c_void_p(yref_ptr or 0), int(steps), seed, first_qp, first_step,
+                                               float(noise_std), int(polish), C.byref(log) if log is not None else None,
+                                               C.c_void_p(stream or 0)), "mpcq_mimo_run_device")
+
+    def mimo_run_ref_device(self, X_ptr: int, U_ptr: int, sched_ptr: int, sched_len: int, sched_stride: int,
+                            steps: int, seed: int, first_qp: int, first_step: int, noise_std: float,
+                            polish: bool = False, log: _capi.MimoLog | None = None, stream: int | None = None) -> None:
+        """``mimo_run_device`` with a reference schedule of ``sched_len`` blocks of ny values per QP, ``sched_stride``
+        doubles apart (0: one for the batch): control step s is ``mimo_step_ref_device`` on the window
+        ref[i] = sched[min(s + i, sched_len - 1)], i < N."""
+        self.solve_count += 1
+        _capi.check(lib().mpcq_mimo_run_ref_device(self._ctx, C.c_void_p(X_ptr or 0), C.c_void_p(U_ptr or 0),
+                                                   C.c_void_p(sched_ptr or 0), int(sched_len), int(sched_stride),
+                                                   int(steps), seed, first_qp, first_step, float(noise_std),
+                                                   int(polish), C.byref(log) if log is not None else None,
+                                                   C.c_void_p(stream or 0)), "mpcq_mimo_run_ref_device")
+
+    def mimo_rollout(self, X, U, steps: int, seed: int, noise_std: float, yref=None, sched=None, polish: bool = False,
+                     first_qp: int = 0, first_step: int = 0, Ad=None, Bd=None) -> dict:
+        """One recorded closed-loop MIMO run from host X (batch, nx), U (batch, nu).  ``sched`` of shape (L, ny) is one
+        reference schedule shared by the batch, (batch, L, ny) one per QP (``mimo_run_ref_device``); without it every
+        step uses ``yref`` (ny values, None: 0; ``mimo_run_device``).  ``Ad`` (batch, nx, nx) and ``Bd`` (batch, nx, nu),
+        when given, set the simulated plant first.  Returns numpy arrays ``U`` (steps, batch, nu), ``X`` (steps, batch,
+        nx), ``status``, ``iter`` (steps, batch) -- row k: control step first_step + k -- ``iters_total``,
+        ``unsolved_total`` (batch,), and the final ``X_final`` (batch, nx), ``U_final`` (batch, nu)."""
+        import torch
+
+        self._mimo_ref_len()  # (refuses a solver without MIMO plants)
+        B, nx, nu, ny, steps = self.batch, self.nx, self.nu, self.ny, int(steps)
+        if (Ad is None) != (Bd is None):
+            raise ValueError("mimo_rollout: Ad and Bd are given together")
+        if sched is not None and yref is not None:
+            raise ValueError("mimo_rollout: yref or sched, not both")
+        dev = torch.device("cuda", self.device)
+        put = lambda a, shape: torch.from_numpy(_c64(a).reshape(shape).copy()).to(dev)
+        Xd, Ud = put(X, (B, nx)), put(U, (B, nu))
+        rows = max(steps, 1)
+        lU = torch.zeros(rows, B, nu, dtype=torch.float64, device=dev)
+        lX = torch.zeros(rows, B, nx, dtype=torch.float64, device=dev)
+        lS, lI = (torch.zeros(rows, B, dtype=torch.int32, device=dev) for _ in range(2))
+        tI, tU = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
+        log = self.mimo_log(lU.data_ptr(), lX.data_ptr(), lS.data_ptr(), lI.data_ptr(), tI.data_ptr(), tU.data_ptr(),
+                            rows, first_step)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if Ad is not None:
+            plant = put(Ad, (B, nx, nx)), put(Bd, (B, nx, nu))
+            self.mimo_set_plant_device(plant[0].data_ptr(), plant[1].data_ptr(), stream)
+        if sched is not None:
+            sc = _c64(sched)
+            if sc.ndim == 2 and sc.shape[1] == ny:
+                stride = 0
+            elif sc.ndim == 3 and sc.shape[0] == B and sc.shape[2] == ny:
+                stride = sc.shape[1] * ny
+            else:
+                raise ValueError(f"sched of shape {sc.shape}: (L, {ny}) or ({B}, L, {ny})")
+            sd = torch.from_numpy(sc.copy()).to(dev)
+            self.mimo_run_ref_device(Xd.data_ptr(), Ud.data_ptr(), sd.data_ptr(), sc.shape[-2], stride, steps, seed,
+                                     first_qp, first_step, noise_std, polish, log, stream)
+        else:
+            yd = put(yref, (ny,)) if yref is not None else None
+            self.mimo_run_device(Xd.data_ptr(), Ud.data_ptr(), yd.data_ptr() if yd is not None else 0, steps, seed,
+                                 first_qp, first_step, noise_std, polish, log, stream)
+        torch.cuda.synchronize(dev)
+        host = lambda t: t.cpu().numpy()
+        return {"U": host(lU[:steps]), "X": host(lX[:steps]), "status": host(lS[:steps]), "iter": host(lI[:steps]),
+                "iters_total": host(tI), "unsolved_total": host(tU), "X_final": host(Xd), "U_final": host(Ud)}
+
     # -- active-set sensitivities of the last MIMO step (mpcq_mimo_sensitivity*, mpcq_mimo_step_*; DESIGN.md 4.15)
     def mimo_sensitivity(self, g=None, n_rhs: int | None = None):
         """(gq, gu, n_active) of the last ``mimo_step_device``: ``g`` of shape (batch, n_rhs, n) (or (batch, n) for one

@@ -29,6 +29,7 @@ EXPORTS = (
     "mpcq_mimo_step_polish_device", "mpcq_mimo_plant_vjp_device", "mpcq_mimo_plant_vjp",
     "mpcq_mimo_step_ref_device", "mpcq_mimo_step_ref", "mpcq_mimo_step_ref_vjp_device",
     "mpcq_mimo_step_ref_gains_device", "mpcq_mimo_step_ref_gains",
+    "mpcq_mimo_set_plant_device", "mpcq_mimo_simulate_device", "mpcq_mimo_run_device", "mpcq_mimo_run_ref_device",
 )
 # The symbols whose names follow OSQP's capitals (osqp_update_P_A).  They are kept apart from EXPORTS because the
 # header scan of tests/test_abi.py, which EXPORTS must equal, reads lower-case names only; lib() binds them with
@@ -68,6 +69,13 @@ class DeviceView(C.Structure):
 class StreamLog(C.Structure):
     """mpcq_stream_log: the per-step record of a receding-horizon stream (device pointers; rows, step0)."""
     _fields_ = [("U", C.c_void_p), ("X", C.c_void_p), ("status", C.c_void_p), ("iter", C.c_void_p),
+                ("rows", C.c_longlong), ("step0", C.c_longlong)]
+
+
+class MimoLog(C.Structure):
+    """mpcq_mimo_log: the record of a closed-loop MIMO run (device pointers; rows, step0)."""
+    _fields_ = [("U", C.c_void_p), ("X", C.c_void_p), ("status", C.c_void_p), ("iter", C.c_void_p),
+                ("iters_total", C.c_void_p), ("unsolved_total", C.c_void_p),
                 ("rows", C.c_longlong), ("step0", C.c_longlong)]
 
 
@@ -122,6 +130,12 @@ def lib() -> C.CDLL:
         "mpcq_mimo_step_ref_gains": (C.c_int, [vp, dp, dp, dp, ip]),
         "mpcq_mimo_plant_vjp_device": (C.c_int, [vp, vp] + [vp] * 9 + [vp] * 3 + [vp] * 9 + [vp, vp]),
         "mpcq_mimo_plant_vjp": (C.c_int, [vp, dp] + [dp] * 9 + [dp] * 3 + [dp] * 9 + [ip]),
+        "mpcq_mimo_set_plant_device": (C.c_int, [vp, vp, vp, vp]),
+        "mpcq_mimo_simulate_device": (C.c_int, [vp, vp, vp, C.c_ulonglong, C.c_longlong, C.c_longlong, C.c_double, vp]),
+        "mpcq_mimo_run_device": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_ulonglong, C.c_longlong, C.c_longlong,
+                                           C.c_double, C.c_int, C.POINTER(MimoLog), vp]),
+        "mpcq_mimo_run_ref_device": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_ulonglong,
+                                               C.c_longlong, C.c_longlong, C.c_double, C.c_int, C.POINTER(MimoLog), vp]),
         "mpcq_get_path": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "mpcq_get_stream_path": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "mpcq_get_order": (C.c_int, [vp, C.POINTER(C.c_int), ip]),

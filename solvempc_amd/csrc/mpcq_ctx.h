@@ -205,6 +205,11 @@ struct mpcq_ctx {
     // mpcq_mimo_plant_vjp*: mimo_sens_kernel's (gq, gu, n_active) for the call's g, which mimo_plant_vjp_kernel reads
     // (batch*n, batch*2n doubles, then batch ints; allocated on first use)
     DevBuf<double> d_mimo_pv;
+    // closed-loop MIMO runs (mpcq_mimo_set_plant_device, mpcq_mimo_run*_device): the simulated plant
+    // of every QP (mimo_plant: set, for the context's mimo_nx, mimo_nu) and the padded tail of a reference schedule
+    // (grown by the first run that reaches it)
+    DevBuf<double> d_mimo_Ad, d_mimo_Bd, d_mimo_tail;
+    bool mimo_plant = false;
     // receding-horizon stream counters (mpcq_mpc_run_device): per-QP iterations and unsolved steps
     DevBuf<int> d_it_acc, d_uns_acc;
     bool stream_acc = false;  // launches made inside mpcq_mpc_run_device accumulate into them

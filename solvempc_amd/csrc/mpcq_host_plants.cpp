@@ -359,6 +359,11 @@ int mpcq_mimo_setup_plants_device(mpcq_ctx *c, int nx, int nu, int ny, int s_row
     const int N = n / nu;
     const mpcq::MimoLayout L = mpcq::MimoLayout::make(N, nx, nu, ny);
     if (c->mimo_N != N || c->mimo_nx != nx || c->mimo_nu != nu || c->mimo_ny != ny) c->d_mimo.release();
+    if (c->mimo_nx != nx || c->mimo_nu != nu) {  // (the simulated plant of mpcq_mimo_set_plant_device has these shapes)
+        c->d_mimo_Ad.release();
+        c->d_mimo_Bd.release();
+        c->mimo_plant = false;
+    }
     if ((rc = c->d_mimo.alloc(8 * (size_t)L.total * c->dims.n_plants, "mimo operator blocks"))) return rc;
     c->mimo_N = N; c->mimo_nx = nx; c->mimo_nu = nu; c->mimo_ny = ny; c->mimo_srows = s_rows;
     c->mode = mpcq_ctx::Mode::None;
@@ -580,6 +585,172 @@ int mpcq_mimo_step_ref(mpcq_ctx *c, const double *X, double *U, const double *re
     if ((rc = polish ? mimo_step_polish_enqueue(c, dX, dU, r, c->last) : mimo_step_enqueue(c, dX, dU, r, c->last)))
         return rc;
     return d2h(c, U, dU, 8 * B * nu);
+}
+
+}  // extern "C"
+
+// ---- closed-loop MIMO runs: the existing step, launched once per control step, and
+// mpcq_mimo_run.hip's plant kernel between two steps
+namespace {
+
+// A MIMO context with a simulated plant (MPCQ_ERR_ORDER otherwise)
+int mimo_plant_check(mpcq_ctx *c, const char *fn)
+{
+    int rc = check_ctx(c, kNone);
+    if (rc) return rc;
+    if (c->mode != mpcq_ctx::Mode::Mimo) return fail(MPCQ_ERR_ORDER, "mpcq_mimo_setup_plants_device has not succeeded");
+    if (!c->mimo_plant)
+        return fail(MPCQ_ERR_ORDER, std::string(fn) + ": no simulated plant (mpcq_mimo_set_plant_device) for this setup's n_x, n_u");
+    return MPCQ_OK;
+}
+
+// One plant update of every QP at absolute control step `step`; with a log, the step's record row and totals
+int mimo_plant_enqueue(mpcq_ctx *c, double *X, const double *U, unsigned long long seed, long long first_qp,
+                       long long step, double noise_std, const mpcq_mimo_log *log, hipStream_t s)
+{
+    mpcq::MimoPlantArgs a{};
+    a.batch = c->dims.batch;
+    a.nx = c->mimo_nx; a.nu = c->mimo_nu;
+    a.Ad = c->d_mimo_Ad; a.Bd = c->d_mimo_Bd;
+    a.X = X; a.U = U;
+    a.seed = seed; a.first_qp = first_qp; a.step = step; a.noise_std = noise_std;
+    a.status = c->d_status; a.iter = c->d_iter;
+    if (log) {
+        const size_t B = c->dims.batch, row = (size_t)(step - log->step0) * B;
+        a.log_U = log->U ? log->U + row * a.nu : nullptr;
+        a.log_X = log->X ? log->X + row * a.nx : nullptr;
+        a.log_status = log->status ? log->status + row : nullptr;
+        a.log_iter = log->iter ? log->iter + row : nullptr;
+        a.iters_total = log->iters_total;
+        a.unsolved_total = log->unsolved_total;
+    }
+    const int lr = mpcq_internal_mimo_plant_launch(&a, s);
+    if (lr) return fail(lr == -1 ? MPCQ_ERR_ARG : MPCQ_ERR_HIP, "mimo plant kernel launch failed");
+    return MPCQ_OK;
+}
+
+// The refusals of a run, before anything is enqueued or written (include/mpcq.h)
+int mimo_run_check(mpcq_ctx *c, const char *fn, const double *X, const double *U, int steps, long long first_step,
+                   int polish, const mpcq_mimo_log *log, hipStream_t s)
+{
+    int rc = check_ctx(c, kNone);
+    if (rc) return rc;
+    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal(fn));
+    if ((rc = mimo_plant_check(c, fn))) return rc;
+    if (!X || !U) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null X/U");
+    if (steps < 0 || first_step < 0) return fail(MPCQ_ERR_ARG, std::string(fn) + ": steps >= 0, first_step >= 0");
+    if (polish != 0 && polish != 1) return fail(MPCQ_ERR_ARG, std::string(fn) + ": polish is 0 or 1");
+    if (log && (log->U || log->X || log->status || log->iter)) {
+        if (log->rows < 1 || log->step0 < 0) return fail(MPCQ_ERR_ARG, std::string(fn) + ": log with rows < 1 or step0 < 0");
+        if (steps > 0 && (first_step < log->step0 || first_step + steps - 1 - log->step0 >= log->rows))
+            return fail(MPCQ_ERR_ARG, std::string(fn) + ": a control step of the call falls outside the log's rows");
+    }
+    return refuse_capture(fn, s);
+}
+
+// `steps` rounds of [control step; plant update].  sched == NULL: every step is mpcq_mimo_step(_polish)_device(yref);
+// otherwise step s is mpcq_mimo_step_ref_device on the window of the schedule that starts at block s, last block held:
+// the schedule itself while s + N <= sched_len, else the padded tail (2N-1 blocks per schedule row from block
+// base = max(sched_len - N, 0), mimo_sched_tail_kernel, built once here) at block min(s - base, N-1).
+int mimo_run_enqueue(mpcq_ctx *c, double *X, double *U, const double *yref, const double *sched, long long sched_len,
+                     long long sched_stride, int steps, unsigned long long seed, long long first_qp,
+                     long long first_step, double noise_std, int polish, const mpcq_mimo_log *log, hipStream_t s)
+{
+    if (steps == 0) return MPCQ_OK;
+    int rc = MPCQ_OK;
+    const size_t B = c->dims.batch;
+    const long long N = c->mimo_N, ny = c->mimo_ny, blocks = 2 * N - 1, base = std::max(sched_len - N, 0ll);
+    const double *tail = nullptr;
+    if (sched && first_step + steps - 1 + N > sched_len) {
+        mpcq::MimoTailArgs t{};
+        t.rows = sched_stride ? (long long)B : 1;
+        t.stride = sched_stride;
+        t.len = sched_len; t.base = base;
+        t.blocks = (int)blocks; t.ny = (int)ny;
+        t.sched = sched;
+        if ((rc = c->d_mimo_tail.grow(8 * (size_t)(t.rows * blocks * ny), s, "mimo schedule tail"))) return rc;
+        tail = t.tail = c->d_mimo_tail;
+        const int lr = mpcq_internal_mimo_sched_tail_launch(&t, s);
+        if (lr) return fail(lr == -1 ? MPCQ_ERR_ARG : MPCQ_ERR_HIP, "mimo schedule tail kernel launch failed");
+    }
+    if (log && log->iters_total) HIPCHK(hipMemsetAsync(log->iters_total, 0, 4 * B, s));
+    if (log && log->unsolved_total) HIPCHK(hipMemsetAsync(log->unsolved_total, 0, 4 * B, s));
+    for (int k = 0; k < steps; k++) {
+        const long long step = first_step + k;
+        MimoRef r;
+        if (!sched) {
+            r.yref = yref;
+        } else if (step + N <= sched_len) {
+            r.ref = sched + step * ny; r.stride = sched_stride; r.horizon = true;
+        } else {
+            r.ref = tail + std::min(step - base, N - 1) * ny;
+            r.stride = sched_stride ? blocks * ny : 0;
+            r.horizon = true;
+        }
+        if ((rc = polish ? mimo_step_polish_enqueue(c, X, U, r, s) : mimo_step_enqueue(c, X, U, r, s))) return rc;
+        if ((rc = mimo_plant_enqueue(c, X, U, seed, first_qp, step, noise_std, log, s))) return rc;
+    }
+    return MPCQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpcq_mimo_set_plant_device(mpcq_ctx *c, const double *Ad, const double *Bd, void *stream)
+{
+    const char *fn = "mpcq_mimo_set_plant_device";
+    int rc = check_ctx(c, kNone);
+    if (rc) return rc;
+    if (c->mode != mpcq_ctx::Mode::Mimo) return fail(MPCQ_ERR_ORDER, "mpcq_mimo_setup_plants_device has not succeeded");
+    if (!Ad || !Bd) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null Ad/Bd");
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = refuse_capture(fn, s))) return rc;
+    const size_t B = c->dims.batch, nx = c->mimo_nx, nu = c->mimo_nu;
+    // (both buffers are released whenever a MIMO setup changes n_x or n_u, so an allocated one has this size)
+    if ((rc = c->d_mimo_Ad.alloc(8 * B * nx * nx, "mimo simulated plant")) ||
+        (rc = c->d_mimo_Bd.alloc(8 * B * nx * nu, "mimo simulated plant")))
+        return rc;
+    HIPCHK(hipMemcpyAsync(c->d_mimo_Ad, Ad, 8 * B * nx * nx, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_mimo_Bd, Bd, 8 * B * nx * nu, hipMemcpyDeviceToDevice, s));
+    c->mimo_plant = true;
+    return MPCQ_OK;
+}
+
+int mpcq_mimo_simulate_device(mpcq_ctx *c, double *X, const double *U, unsigned long long seed, long long first_qp,
+                              long long step, double noise_std, void *stream)
+{
+    const char *fn = "mpcq_mimo_simulate_device";
+    int rc = mimo_plant_check(c, fn);
+    if (rc) return rc;
+    if (!X || !U) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null X/U");
+    if (step < 0) return fail(MPCQ_ERR_ARG, std::string(fn) + ": step >= 0");
+    return mimo_plant_enqueue(c, X, U, seed, first_qp, step, noise_std, nullptr, (hipStream_t)stream);
+}
+
+int mpcq_mimo_run_device(mpcq_ctx *c, double *X, double *U, const double *yref, int steps, unsigned long long seed,
+                         long long first_qp, long long first_step, double noise_std, int polish,
+                         const mpcq_mimo_log *log, void *stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    int rc = mimo_run_check(c, "mpcq_mimo_run_device", X, U, steps, first_step, polish, log, s);
+    if (rc) return rc;
+    return mimo_run_enqueue(c, X, U, yref, nullptr, 0, 0, steps, seed, first_qp, first_step, noise_std, polish, log, s);
+}
+
+int mpcq_mimo_run_ref_device(mpcq_ctx *c, double *X, double *U, const double *sched, int sched_len,
+                             long long sched_stride, int steps, unsigned long long seed, long long first_qp,
+                             long long first_step, double noise_std, int polish, const mpcq_mimo_log *log, void *stream)
+{
+    const char *fn = "mpcq_mimo_run_ref_device";
+    hipStream_t s = (hipStream_t)stream;
+    int rc = mimo_run_check(c, fn, X, U, steps, first_step, polish, log, s);
+    if (rc) return rc;
+    if (!sched || sched_len < 1) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null schedule or sched_len < 1");
+    if (sched_stride != 0 && sched_stride < (long long)sched_len * c->mimo_ny)
+        return fail(MPCQ_ERR_ARG, std::string(fn) + ": sched_stride is 0 (one schedule for the batch) or >= sched_len*n_y");
+    return mimo_run_enqueue(c, X, U, nullptr, sched, sched_len, sched_stride, steps, seed, first_qp, first_step,
+                            noise_std, polish, log, s);
 }
 
 }  // extern "C"

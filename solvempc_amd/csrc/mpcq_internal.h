@@ -476,6 +476,34 @@ struct MimoPlantVjpArgs {
     double *gAd, *gBd, *gCd, *gQ, *gR, *gRD, *gK, *gK0, *gw0;  // [plant] shapes of the plant data; each may be null
     int *n_active;              // [batch] copy of nact (or null)
 };
+
+// Arguments of mimo_plant_kernel (mpcq_mimo_run.hip): one plant update of every QP between two control steps of a
+// closed-loop MIMO run, with the step's record row and totals.  A 16-lane group per QP, fp64.
+struct MimoPlantArgs {
+    int batch, nx, nu;
+    const double *Ad, *Bd;      // [batch] nx*nx, nx*nu: the simulated plant (mpcq_mimo_set_plant_device)
+    double *X;                  // [batch] nx, updated in place
+    const double *U;            // [batch] nu, the control the plant sees
+    unsigned long long seed;
+    long long first_qp, step;   // the noise of QP b at this control step is keyed by (seed, first_qp + b, step)
+    double noise_std;
+    // the record (each may be null): this step's row of mpcq_mimo_log, already offset to the row, and its totals
+    double *log_U, *log_X;      // [batch] nu, nx
+    int *log_status, *log_iter; // [batch]
+    int *iters_total, *unsolved_total;  // [batch] += iter, += (status != SOLVED)
+    const int *status, *iter;   // [batch] the control step's (read only where the record asks for them)
+};
+
+// Arguments of mimo_sched_tail_kernel (mpcq_mimo_run.hip): the padded tail of a reference schedule,
+// tail[r][j] = sched[r][min(base + j, len - 1)] for j < blocks, blocks of ny values.
+struct MimoTailArgs {
+    long long rows;             // schedule rows: batch, or 1 for a shared schedule
+    long long stride;           // doubles between two rows of sched (unused when rows == 1)
+    long long len, base;        // blocks of the schedule; the first block of the tail
+    int blocks, ny;             // 2N - 1 blocks per row
+    const double *sched;
+    double *tail;               // [rows] blocks*ny
+};
 }  // namespace mpcq
 
 namespace mpcq {
@@ -798,6 +826,10 @@ size_t mpcq_internal_mimo_polish_lds(int n);
 // setup accepts), same return codes; its dynamic LDS bytes for the call's N, nx, nu, ny.
 int mpcq_internal_mimo_plant_vjp_launch(const mpcq::MimoPlantVjpArgs *a, int cus, hipStream_t s, hipError_t *err);
 size_t mpcq_internal_mimo_plant_vjp_lds(int N, int nx, int nu, int ny);
+// The plant update, record row and totals of one step of a closed-loop MIMO run, and the padded tail of its
+// reference schedule (mpcq_mimo_run.hip): 0 launched, -1 unsupported shape, -2 HIP error.
+int mpcq_internal_mimo_plant_launch(const mpcq::MimoPlantArgs *a, hipStream_t s);
+int mpcq_internal_mimo_sched_tail_launch(const mpcq::MimoTailArgs *a, hipStream_t s);
 // One pass per batch of distinct SISO plants (mpcq_plant.hip): condensing + setup + one
 // controllerStep per plant, two plants per wave.  0 launched, -1 unsupported shape, -2 HIP error.
 int mpcq_internal_plant_step_launch(const mpcq::PlantStepArgs *a, int is_f32, hipStream_t s);

@@ -59,6 +59,19 @@ def simulate(Ad, Bd, X, U, w) -> np.ndarray:
     return X @ np.asarray(Ad).T + np.asarray(U)[:, None] * np.asarray(Bd)[None, :] + w
 
 
+def simulate_mimo(Ad, Bd, X, U, w) -> np.ndarray:
+    """X_b <- Ad_b X_b + Bd_b U_b + w_b for a batch of MIMO plants, one plant per QP: Ad (B, nx, nx), Bd (B, nx, nu),
+    X, w (B, nx), U (B, nu).  The row mpcq_mimo_simulate_device computes, in its order: the Ad terms in ascending
+    column, then the Bd terms, then w, every product rounded before it is added."""
+    Ad, Bd, X, U = (np.asarray(a, dtype=np.float64) for a in (Ad, Bd, X, U))
+    s = np.zeros_like(X)
+    for t in range(Ad.shape[2]):
+        s = s + Ad[:, :, t] * X[:, t, None]
+    for j in range(Bd.shape[2]):
+        s = s + Bd[:, :, j] * U[:, j, None]
+    return s + w
+
+
 def mpc_states(seed: int, start: int, count: int, u_range: float = 1.0):
     """Config 2 states: X ~ N(0, diag(.1,.1,.05,.5)), U ~ U(-u_range, u_range) (0 when u_range=0)."""
     X = normals(seed, start, count, 4) * X_STD
