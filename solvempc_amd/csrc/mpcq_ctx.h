@@ -196,20 +196,37 @@ struct mpcq_ctx {
     // what the captured step leaves lazy and its order flag: every replay leaves the same, whatever a reader
     // materialised in between
     Lazy glazy;
-    // MIMO condensed MPC (mpcq_mimo.hip): per-plant operator block, dims
-    DevBuf<double> d_mimo;
-    int mimo_N = 0, mimo_nx = 0, mimo_nu = 0, mimo_ny = 0, mimo_srows = 0, mimo_diag_k0 = 0;
     bool mimo_only = false;  // n > 32 or m > 64 per plant: only the MIMO entry points serve it
-    bool mimo_stepped = false;  // a mpcq_mimo_step_device since the last MIMO setup (mpcq_mimo_sensitivity* needs one)
-    bool mimo_ref_step = false; // that step was a mpcq_mimo_step_ref* (mpcq_mimo_plant_vjp* knows yref only: refused)
-    // mpcq_mimo_plant_vjp*: mimo_sens_kernel's (gq, gu, n_active) for the call's g, which mimo_plant_vjp_kernel reads
-    // (batch*n, batch*2n doubles, then batch ints; allocated on first use)
-    DevBuf<double> d_mimo_pv;
-    // closed-loop MIMO runs (mpcq_mimo_set_plant_device, mpcq_mimo_run*_device): the simulated plant
-    // of every QP (mimo_plant: set, for the context's mimo_nx, mimo_nu) and the padded tail of a reference schedule
-    // (grown by the first run that reaches it)
-    DevBuf<double> d_mimo_Ad, d_mimo_Bd, d_mimo_tail;
-    bool mimo_plant = false;
+    // MIMO condensed MPC (mpcq_mimo.hip; the host side is mpcq_host_mimo.cpp): what the last
+    // mpcq_mimo_setup_plants_device left and what the mpcq_mimo_* calls keep between them
+    struct Mimo {
+        DevBuf<double> ops;  // per-plant operator block
+        int N = 0, nx = 0, nu = 0, ny = 0, srows = 0, diag_k0 = 0;  // dims
+        bool stepped = false;  // a mpcq_mimo_step_device since the last MIMO setup (mpcq_mimo_sensitivity* needs one)
+        bool ref_step = false; // that step was a mpcq_mimo_step_ref* (mpcq_mimo_plant_vjp* knows yref only: refused)
+        // mpcq_mimo_plant_vjp*: mimo_sens_kernel's (gq, gu, n_active) for the call's g, which mimo_plant_vjp_kernel reads
+        // (batch*n, batch*2n doubles, then batch ints; allocated on first use)
+        DevBuf<double> pv;
+        // closed-loop MIMO runs (mpcq_mimo_set_plant_device, mpcq_mimo_run*_device): the simulated plant
+        // of every QP (plant: set, for this block's nx, nu) and the padded tail of a reference schedule (grown by the
+        // first run that reaches it)
+        DevBuf<double> Ad, Bd, tail;
+        bool plant = false;
+        DevBuf<double> Uprev;  // mpcq_mimo_step_polish_device: the caller's U from before the step
+        // What a setup for these dims invalidates, whether it then succeeds or not: the operator blocks of another
+        // shape, the simulated plant of another n_x or n_u (mpcq_mimo_set_plant_device's arrays have these shapes), and
+        // every record of a step.
+        void invalidate(int N_, int nx_, int nu_, int ny_)
+        {
+            if (N != N_ || nx != nx_ || nu != nu_ || ny != ny_) ops.release();
+            if (nx != nx_ || nu != nu_) {
+                Ad.release();
+                Bd.release();
+                plant = false;
+            }
+            stepped = ref_step = false;
+        }
+    } mimo;
     // receding-horizon stream counters (mpcq_mpc_run_device): per-QP iterations and unsolved steps
     DevBuf<int> d_it_acc, d_uns_acc;
     bool stream_acc = false;  // launches made inside mpcq_mpc_run_device accumulate into them
@@ -235,10 +252,10 @@ struct mpcq_ctx {
     bool ord_clean = false;  // the order's bin counters are zero (an ordered phase-0 launch clears them)
     // settings.polish (mpcq_polish.hip): status_polish and the reduced system's rows per QP, the returned
     // solution's (primal, dual) residual pairs; allocated only when polish is set, or by the first
-    // mpcq_mimo_step_polish_device (mpcq_mimo_polish.hip), which also keeps the caller's U from before the step in
-    // d_mimo_Uprev.  pol_valid: the last solve filled them (mpcq_get_polish_info reports "not performed" otherwise)
+    // mpcq_mimo_step_polish_device (mpcq_mimo_polish.hip).  pol_valid: the last solve filled them
+    // (mpcq_get_polish_info reports "not performed" otherwise)
     DevBuf<int> d_pol_status, d_pol_nact;
-    DevBuf<double> d_pol_res, d_mimo_Uprev;
+    DevBuf<double> d_pol_res;
     bool pol_valid = false;
     // active-set sensitivities (mpcq_sens.hip).  sens_ok: the warm state and d_l, d_u are those of a solve that
     // mpcq_sensitivity* serves (set by launch_solve outside a stream run; cleared by every setup, data update,
@@ -297,6 +314,7 @@ mpcq::SolverSettings to_solver(const mpcq_settings &s);
 template <typename T>
 mpcq::AdmmArgs<T> make_args(mpcq_ctx *c);  // (instantiated for float and double)
 int dump_tile_stamps(const char *path, const long long *d_stamps, size_t phases, size_t waves, hipStream_t s);
+int dump_stamps(const char *path, const long long *d_stamps, size_t count, hipStream_t s);
 void verbose_header(const mpcq_ctx *c, const char *what);
 void verbose_solve(mpcq_ctx *c, double seconds);
 int launch_solve(mpcq_ctx *c, hipStream_t s, bool mpc, const double *X, double *U, double xref);
@@ -319,5 +337,43 @@ void set_mpc_front_end(const mpcq_ctx *c, mpcq::AdmmArgs<T> &a, const double *X,
     a.mpc = 1; a.mpc_u = 1; a.nx = c->nx; a.X = X; a.U = U; a.xref = xref;
     set_front_end_ops(c, a);
 }
+
+// ---- MIMO (mpcq_host_mimo.cpp)
+// The MIMO setup's dims and operator blocks, on any of the per-QP argument structs (MimoArgs, MimoSensArgs,
+// MimoPolishArgs, MimoPlantVjpArgs); those with s_rows add it themselves.
+template <typename A>
+void set_mimo_ops(const mpcq_ctx *c, A &a)
+{
+    a.batch = c->dims.batch;
+    a.N = c->mimo.N; a.nx = c->mimo.nx; a.nu = c->mimo.nu; a.ny = c->mimo.ny;
+    a.ops_stride = (size_t)mpcq::MimoLayout::make(a.N, a.nx, a.nu, a.ny).total;
+    a.ops = c->mimo.ops;
+}
+
+// The device staging of one host-form call: one allocation handed out as consecutive typed sub-arrays.  The
+// stream is waited for, whatever the outcome, before the staging goes away.
+class Staging {
+    DevBuf<double> d_;
+    double *next_ = nullptr;
+    hipStream_t s_;
+
+public:
+    explicit Staging(hipStream_t s) : s_(s) {}
+    ~Staging() { (void)hipStreamSynchronize(s_); }
+    int alloc(size_t doubles, const char *what)
+    {
+        const int rc = d_.alloc(8 * doubles, what);
+        next_ = d_;
+        return rc;
+    }
+    // The next `doubles` doubles, read as T (ints: two to a double, an odd count rounded up by the caller)
+    template <typename T = double>
+    T *take(size_t doubles)
+    {
+        double *p = next_;
+        next_ += doubles;
+        return (T *)p;
+    }
+};
 
 #pragma GCC visibility pop

@@ -1,5 +1,5 @@
 // solvempc_amd/csrc/mpcq_host_plants.cpp — host side of the C ABI declared in include/mpcq.h: condensing and its
-// VJP, the per-plant MPC setup and one-pass step, the MIMO setup and step.
+// VJP, the per-plant MPC setup and one-pass step.
 #include "mpcq_ctx.h"
 
 namespace {
@@ -323,15 +323,7 @@ int mpcq_mpc_plants_step_device(mpcq_ctx *c, int nx, int s_rows, const double *A
     }
     const int lr = mpcq_internal_plant_step_launch(&a, c->dims.dtype == MPCQ_F32, s);
     if (lr) return fail(lr == -1 ? MPCQ_ERR_ARG : MPCQ_ERR_HIP, "plants_step kernel launch failed");
-    if (pst && *pst) {
-        std::vector<long long> h(16 * nwaves);
-        HIPCHK(hipMemcpyAsync(h.data(), c->d_stamps, 8 * h.size(), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (FILE *f = std::fopen(pst, "wb")) {
-            std::fwrite(h.data(), 8, h.size(), f);
-            std::fclose(f);
-        }
-    }
+    if (pst && *pst && (rc = dump_stamps(pst, c->d_stamps, 16 * nwaves, s))) return rc;
     if (ordered) c->ord_clean = true;
     c->lazy.ord = ordered;
     c->mode = mpcq_ctx::Mode::OneShot;  // results only: no operator blocks were written
@@ -339,418 +331,6 @@ int mpcq_mpc_plants_step_device(mpcq_ctx *c, int nx, int s_rows, const double *A
     c->mpc_ready = false;
     c->last = s;
     return MPCQ_OK;
-}
-
-int mpcq_mimo_setup_plants_device(mpcq_ctx *c, int nx, int nu, int ny, int s_rows, const double *Ad, const double *Bd,
-                                  const double *Cd, const double *Q, const double *R, const double *RD, const double *K,
-                                  const double *K0, const double *w0, void *stream)
-{
-    int rc = check_ctx(c, kNone);
-    if (rc) return rc;
-    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal("mpcq_mimo_setup_plants_device"));
-    if ((rc = materialize_xy(c))) return rc;  // (the operator blocks below replace the tile images' role)
-    const int n = c->dims.n, m = c->dims.m;
-    if (nu != 1 && nu != 2 && nu != 4) return fail(MPCQ_ERR_ARG, "mimo: n_u must be 1, 2 or 4");
-    if (nx <= 0 || nx > 12 || ny <= 0 || ny > 12 || s_rows < 0) return fail(MPCQ_ERR_ARG, "mimo: 1 <= n_x, n_y <= 12");
-    if (n % nu || n / nu > 32 || n > 128 || m != 2 * n) return fail(MPCQ_ERR_ARG, "mimo: n = N n_u <= 128 (N <= 32), m = 2n");
-    if (c->dims.n_plants != c->dims.batch || c->dims.dtype == MPCQ_F32)
-        return fail(MPCQ_ERR_ARG, "mimo: one plant per QP (n_plants == batch), dtype MPCQ_F64 or MPCQ_F64_MIXED");
-    if (!Ad || !Bd || !Cd || !Q || !R || !RD || !K || !K0 || !w0) return fail(MPCQ_ERR_ARG, "mimo: null plant array");
-    const int N = n / nu;
-    const mpcq::MimoLayout L = mpcq::MimoLayout::make(N, nx, nu, ny);
-    if (c->mimo_N != N || c->mimo_nx != nx || c->mimo_nu != nu || c->mimo_ny != ny) c->d_mimo.release();
-    if (c->mimo_nx != nx || c->mimo_nu != nu) {  // (the simulated plant of mpcq_mimo_set_plant_device has these shapes)
-        c->d_mimo_Ad.release();
-        c->d_mimo_Bd.release();
-        c->mimo_plant = false;
-    }
-    if ((rc = c->d_mimo.alloc(8 * (size_t)L.total * c->dims.n_plants, "mimo operator blocks"))) return rc;
-    c->mimo_N = N; c->mimo_nx = nx; c->mimo_nu = nu; c->mimo_ny = ny; c->mimo_srows = s_rows;
-    c->mode = mpcq_ctx::Mode::None;
-    c->sens_ok = false;
-    c->mimo_stepped = false;
-    c->mimo_ref_step = false;
-    c->pol_valid = false;
-    c->gen++;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemsetAsync(c->d_flags, 0, 4, s));
-    mpcq::MimoSetupArgs a{};
-    a.n_plants = c->dims.n_plants;
-    a.N = N; a.nx = nx; a.nu = nu; a.ny = ny; a.s_rows = s_rows;
-    a.scaling = c->set.scaling;
-    a.sigma = c->set.sigma;
-    a.Ad = Ad; a.Bd = Bd; a.Cd = Cd; a.Q = Q; a.R = R; a.RD = RD; a.K = K; a.K0 = K0; a.w0 = w0;
-    a.ops = c->d_mimo;
-    a.flags = c->d_flags;
-    const char *sst = debug_hook("MPCQ_MIMO_SETUP_STAMPS");  // per-plant phase stamps
-    if (sst && *sst) {
-        c->d_stamps.release();
-        if ((rc = c->d_stamps.alloc(8 * 16 * (size_t)a.n_plants, "stamps"))) return rc;
-        a.stamps = c->d_stamps;
-    }
-    const int lr = mpcq_internal_mimo_setup_launch(&a, s);
-    if (lr == -1) return fail(MPCQ_ERR_ARG, "mimo: shape beyond the setup kernel's LDS capacity");
-    if (lr) return fail(MPCQ_ERR_HIP, std::string("mimo setup launch failed: ") + hipGetErrorString(hipGetLastError()));
-    int flags = 0;
-    HIPCHK(hipMemcpyAsync(&flags, c->d_flags, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (sst && *sst) {
-        std::vector<long long> h(16 * (size_t)a.n_plants);
-        HIPCHK(hipMemcpy(h.data(), c->d_stamps, 8 * h.size(), hipMemcpyDeviceToHost));
-        c->d_stamps.release();
-        if (FILE *f = std::fopen(sst, "wb")) {
-            std::fwrite(h.data(), 8, h.size(), f);
-            std::fclose(f);
-        }
-    }
-    if (flags & 1) return fail(MPCQ_ERR_SETUP, "mimo: P + sigma I is not positive definite (non-convex QP)");
-    if (flags & 2) return fail(MPCQ_ERR_SETUP, "mimo: a constraint row is not an inequality (|w0| beyond OSQP_INFTY)");
-    c->mimo_diag_k0 = (flags & 4) ? 0 : 1;
-    c->last = s;
-    c->fresh = true;  // the first step starts from x = z = y = 0, rho = settings.rho (initSolver, :64)
-    c->mpc_ready = false;  // the generic front-end operators no longer describe this context
-    c->mode = mpcq_ctx::Mode::Mimo;
-    return MPCQ_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// The reference of one MIMO step: yref (n_y values for the whole batch, held over the horizon; NULL: 0) of
-// mpcq_mimo_step_device, or with `horizon` a horizon of N*n_y values per QP, `stride` doubles apart (0: one for the
-// batch), of mpcq_mimo_step_ref_device
-struct MimoRef {
-    const double *yref = nullptr, *ref = nullptr;
-    long long stride = 0;
-    bool horizon = false;
-};
-
-// The refusals of a MIMO step, in the order of include/mpcq.h, before anything is enqueued or written
-int mimo_step_check(mpcq_ctx *c, const char *fn, const double *X, const double *U, const MimoRef &r, bool polish,
-                    hipStream_t s)
-{
-    int rc = check_ctx(c, kNone);
-    if (rc) return rc;
-    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal(fn));
-    if (c->mode != mpcq_ctx::Mode::Mimo) return fail(MPCQ_ERR_ORDER, "mpcq_mimo_setup_plants_device has not succeeded");
-    if (!X || !U) return fail(MPCQ_ERR_ARG, "null X/U");
-    if (r.horizon) {
-        if (!r.ref) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null ref");
-        if (r.stride != 0 && r.stride < (long long)c->mimo_N * c->mimo_ny)
-            return fail(MPCQ_ERR_ARG, std::string(fn) + ": ref_stride is 0 (one reference for the batch) or >= N*n_y");
-    }
-    return polish ? refuse_capture(fn, s) : MPCQ_OK;
-}
-
-int mimo_step_enqueue(mpcq_ctx *c, const double *X, double *U, const MimoRef &r, void *stream)
-{
-    int rc = materialize_xy(c);  // (a pending lazy x, y first: the kernel below rewrites the state)
-    if (rc) return rc;
-    mpcq::MimoArgs a{};
-    a.batch = c->dims.batch;
-    a.N = c->mimo_N; a.nx = c->mimo_nx; a.nu = c->mimo_nu; a.ny = c->mimo_ny; a.s_rows = c->mimo_srows;
-    a.diag_k0 = c->mimo_diag_k0 && !*test_hook("MPCQ_MIMO_GENERAL_K0");
-    a.ops_stride = (size_t)mpcq::MimoLayout::make(a.N, a.nx, a.nu, a.ny).total;
-    a.ops = c->d_mimo;
-    a.st = to_solver(c->set);
-    const int ct = c->set.check_termination;
-    a.adaptive_interval = c->set.adaptive_rho_interval ? c->set.adaptive_rho_interval : (ct ? 4 * ct : 100);
-    a.X = X; a.U = U; a.yref = r.horizon ? nullptr : r.yref;
-    a.q_out = c->d_q; a.u_out = c->d_u;
-    a.xs = (double *)c->d_xs; a.zs = (double *)c->d_zs; a.ys = (double *)c->d_ys; a.rhos = (double *)c->d_rhos;
-    a.warm = c->set.warm_start;
-    a.fresh = c->fresh;
-    a.x = c->d_x; a.y = c->d_y; a.status = c->d_status; a.iter = c->d_iter; a.rho_out = c->d_rho;
-    const char *stp = debug_hook("MPCQ_MIMO_STAMPS");  // per-QP stage stamps
-    if (stp && *stp) {
-        if ((rc = c->d_stamps.alloc(8 * 8 * (size_t)a.batch, "stamps"))) return rc;
-        a.stamps = c->d_stamps;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const int lr = r.horizon ? mpcq_internal_mimo_solve_ref_launch(&a, r.ref, r.stride, s)
-                             : mpcq_internal_mimo_solve_launch(&a, s);
-    if (lr) return fail(lr == -1 ? MPCQ_ERR_ARG : MPCQ_ERR_HIP, "mimo solve launch failed");
-    if (stp && *stp) {
-        std::vector<long long> h(8 * (size_t)a.batch);
-        HIPCHK(hipMemcpyAsync(h.data(), c->d_stamps, 8 * h.size(), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (FILE *f = std::fopen(stp, "wb")) {
-            std::fwrite(h.data(), 8, h.size(), f);
-            std::fclose(f);
-        }
-    }
-    c->last = s;
-    c->fresh = false;
-    c->mimo_stepped = true;
-    c->mimo_ref_step = r.horizon;
-    c->pol_valid = false;
-    return MPCQ_OK;
-}
-
-// The step, then OSQP's polish of every SOLVED QP on the same stream (mpcq_mimo_polish.hip)
-int mimo_step_polish_enqueue(mpcq_ctx *c, const double *X, double *U, const MimoRef &r, void *stream)
-{
-    int rc = MPCQ_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t B = c->dims.batch, nu = c->mimo_nu;
-    if ((rc = c->d_pol_status.alloc(4 * B)) || (rc = c->d_pol_nact.alloc(4 * B)) || (rc = c->d_pol_res.alloc(8 * 2 * B)) ||
-        (rc = c->d_mimo_Uprev.grow(8 * B * nu, s, "mimo polish staging")))
-        return rc;
-    HIPCHK(hipMemcpyAsync(c->d_mimo_Uprev, U, 8 * B * nu, hipMemcpyDeviceToDevice, s));
-    if ((rc = mimo_step_enqueue(c, X, U, r, stream))) return rc;
-    mpcq::MimoPolishArgs a{};
-    a.batch = c->dims.batch;
-    a.N = c->mimo_N; a.nx = c->mimo_nx; a.nu = c->mimo_nu; a.ny = c->mimo_ny;
-    a.ops_stride = (size_t)mpcq::MimoLayout::make(a.N, a.nx, a.nu, a.ny).total;
-    a.ops = c->d_mimo;
-    a.q = c->d_q; a.u = c->d_u;
-    a.xs = (double *)c->d_xs; a.zs = (double *)c->d_zs; a.ys = (double *)c->d_ys;
-    a.status = c->d_status;
-    a.x = c->d_x; a.y = c->d_y;
-    a.U_prev = c->d_mimo_Uprev; a.U = U;
-    a.pol_status = c->d_pol_status; a.pol_nact = c->d_pol_nact; a.pol_res = c->d_pol_res;
-    a.delta = c->set.delta;
-    a.refine = c->set.polish_refine_iter;
-    a.scaled_termination = c->set.scaled_termination;
-    hipError_t err = hipSuccess;
-    const int lr = mpcq_internal_mimo_polish_launch(&a, c->cus, s, &err);
-    if (lr == -1) return fail(MPCQ_ERR_ARG, "mimo polish: shape beyond the kernel's capacity");
-    if (lr) return fail(MPCQ_ERR_HIP, std::string("mimo polish kernel launch failed: ") + hipGetErrorString(err));
-    c->pol_valid = true;
-    return MPCQ_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int mpcq_mimo_step_device(mpcq_ctx *c, const double *X, double *U, const double *yref, void *stream)
-{
-    MimoRef r;
-    r.yref = yref;
-    int rc = mimo_step_check(c, "mpcq_mimo_step_device", X, U, r, false, (hipStream_t)stream);
-    if (rc) return rc;
-    return mimo_step_enqueue(c, X, U, r, stream);
-}
-
-int mpcq_mimo_step_polish_device(mpcq_ctx *c, const double *X, double *U, const double *yref, void *stream)
-{
-    MimoRef r;
-    r.yref = yref;
-    int rc = mimo_step_check(c, "mpcq_mimo_step_polish_device", X, U, r, true, (hipStream_t)stream);
-    if (rc) return rc;
-    return mimo_step_polish_enqueue(c, X, U, r, stream);
-}
-
-int mpcq_mimo_step_ref_device(mpcq_ctx *c, const double *X, double *U, const double *ref, long long ref_stride,
-                              int polish, void *stream)
-{
-    const char *fn = "mpcq_mimo_step_ref_device";
-    if (polish != 0 && polish != 1) return fail(MPCQ_ERR_ARG, std::string(fn) + ": polish is 0 or 1");
-    MimoRef r;
-    r.ref = ref; r.stride = ref_stride; r.horizon = true;
-    int rc = mimo_step_check(c, fn, X, U, r, polish == 1, (hipStream_t)stream);
-    if (rc) return rc;
-    return polish ? mimo_step_polish_enqueue(c, X, U, r, stream) : mimo_step_enqueue(c, X, U, r, stream);
-}
-
-int mpcq_mimo_step_ref(mpcq_ctx *c, const double *X, double *U, const double *ref, long long ref_stride, int polish)
-{
-    const char *fn = "mpcq_mimo_step_ref";
-    if (polish != 0 && polish != 1) return fail(MPCQ_ERR_ARG, std::string(fn) + ": polish is 0 or 1");
-    MimoRef r;
-    r.ref = ref; r.stride = ref_stride; r.horizon = true;
-    int rc = mimo_step_check(c, fn, X, U, r, polish == 1, c ? c->last : nullptr);
-    if (rc) return rc;
-    const size_t B = c->dims.batch, nx = c->mimo_nx, nu = c->mimo_nu, nr = (size_t)c->mimo_N * c->mimo_ny;
-    const size_t rows = ref_stride ? B : 1;
-    // staging of this call alone: X, U, then the references packed (B rows of N*n_y, or the one shared row)
-    DevBuf<double> d;
-    if ((rc = d.alloc(8 * (B * (nx + nu) + rows * nr), "mimo reference staging"))) return rc;
-    struct Drain {  // (the stream is waited for, whatever the outcome, before the staging goes away)
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{c->last};
-    double *dX = d, *dU = dX + B * nx, *dr = dU + B * nu;
-    if ((rc = h2d(dX, X, 8 * B * nx, c->last)) || (rc = h2d(dU, U, 8 * B * nu, c->last))) return rc;
-    if (rows == 1 || ref_stride == (long long)nr) {
-        if ((rc = h2d(dr, ref, 8 * rows * nr, c->last))) return rc;
-    } else {
-        HIPCHK(hipMemcpy2DAsync(dr, 8 * nr, ref, 8 * (size_t)ref_stride, 8 * nr, rows, hipMemcpyHostToDevice, c->last));
-        HIPCHK(hipStreamSynchronize(c->last));
-    }
-    r.ref = dr;
-    r.stride = ref_stride ? (long long)nr : 0;
-    if ((rc = polish ? mimo_step_polish_enqueue(c, dX, dU, r, c->last) : mimo_step_enqueue(c, dX, dU, r, c->last)))
-        return rc;
-    return d2h(c, U, dU, 8 * B * nu);
-}
-
-}  // extern "C"
-
-// ---- closed-loop MIMO runs: the existing step, launched once per control step, and
-// mpcq_mimo_run.hip's plant kernel between two steps
-namespace {
-
-// A MIMO context with a simulated plant (MPCQ_ERR_ORDER otherwise)
-int mimo_plant_check(mpcq_ctx *c, const char *fn)
-{
-    int rc = check_ctx(c, kNone);
-    if (rc) return rc;
-    if (c->mode != mpcq_ctx::Mode::Mimo) return fail(MPCQ_ERR_ORDER, "mpcq_mimo_setup_plants_device has not succeeded");
-    if (!c->mimo_plant)
-        return fail(MPCQ_ERR_ORDER, std::string(fn) + ": no simulated plant (mpcq_mimo_set_plant_device) for this setup's n_x, n_u");
-    return MPCQ_OK;
-}
-
-// One plant update of every QP at absolute control step `step`; with a log, the step's record row and totals
-int mimo_plant_enqueue(mpcq_ctx *c, double *X, const double *U, unsigned long long seed, long long first_qp,
-                       long long step, double noise_std, const mpcq_mimo_log *log, hipStream_t s)
-{
-    mpcq::MimoPlantArgs a{};
-    a.batch = c->dims.batch;
-    a.nx = c->mimo_nx; a.nu = c->mimo_nu;
-    a.Ad = c->d_mimo_Ad; a.Bd = c->d_mimo_Bd;
-    a.X = X; a.U = U;
-    a.seed = seed; a.first_qp = first_qp; a.step = step; a.noise_std = noise_std;
-    a.status = c->d_status; a.iter = c->d_iter;
-    if (log) {
-        const size_t B = c->dims.batch, row = (size_t)(step - log->step0) * B;
-        a.log_U = log->U ? log->U + row * a.nu : nullptr;
-        a.log_X = log->X ? log->X + row * a.nx : nullptr;
-        a.log_status = log->status ? log->status + row : nullptr;
-        a.log_iter = log->iter ? log->iter + row : nullptr;
-        a.iters_total = log->iters_total;
-        a.unsolved_total = log->unsolved_total;
-    }
-    const int lr = mpcq_internal_mimo_plant_launch(&a, s);
-    if (lr) return fail(lr == -1 ? MPCQ_ERR_ARG : MPCQ_ERR_HIP, "mimo plant kernel launch failed");
-    return MPCQ_OK;
-}
-
-// The refusals of a run, before anything is enqueued or written (include/mpcq.h)
-int mimo_run_check(mpcq_ctx *c, const char *fn, const double *X, const double *U, int steps, long long first_step,
-                   int polish, const mpcq_mimo_log *log, hipStream_t s)
-{
-    int rc = check_ctx(c, kNone);
-    if (rc) return rc;
-    if (c->set.polish) return fail(MPCQ_ERR_ARG, polish_refusal(fn));
-    if ((rc = mimo_plant_check(c, fn))) return rc;
-    if (!X || !U) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null X/U");
-    if (steps < 0 || first_step < 0) return fail(MPCQ_ERR_ARG, std::string(fn) + ": steps >= 0, first_step >= 0");
-    if (polish != 0 && polish != 1) return fail(MPCQ_ERR_ARG, std::string(fn) + ": polish is 0 or 1");
-    if (log && (log->U || log->X || log->status || log->iter)) {
-        if (log->rows < 1 || log->step0 < 0) return fail(MPCQ_ERR_ARG, std::string(fn) + ": log with rows < 1 or step0 < 0");
-        if (steps > 0 && (first_step < log->step0 || first_step + steps - 1 - log->step0 >= log->rows))
-            return fail(MPCQ_ERR_ARG, std::string(fn) + ": a control step of the call falls outside the log's rows");
-    }
-    return refuse_capture(fn, s);
-}
-
-// `steps` rounds of [control step; plant update].  sched == NULL: every step is mpcq_mimo_step(_polish)_device(yref);
-// otherwise step s is mpcq_mimo_step_ref_device on the window of the schedule that starts at block s, last block held:
-// the schedule itself while s + N <= sched_len, else the padded tail (2N-1 blocks per schedule row from block
-// base = max(sched_len - N, 0), mimo_sched_tail_kernel, built once here) at block min(s - base, N-1).
-int mimo_run_enqueue(mpcq_ctx *c, double *X, double *U, const double *yref, const double *sched, long long sched_len,
-                     long long sched_stride, int steps, unsigned long long seed, long long first_qp,
-                     long long first_step, double noise_std, int polish, const mpcq_mimo_log *log, hipStream_t s)
-{
-    if (steps == 0) return MPCQ_OK;
-    int rc = MPCQ_OK;
-    const size_t B = c->dims.batch;
-    const long long N = c->mimo_N, ny = c->mimo_ny, blocks = 2 * N - 1, base = std::max(sched_len - N, 0ll);
-    const double *tail = nullptr;
-    if (sched && first_step + steps - 1 + N > sched_len) {
-        mpcq::MimoTailArgs t{};
-        t.rows = sched_stride ? (long long)B : 1;
-        t.stride = sched_stride;
-        t.len = sched_len; t.base = base;
-        t.blocks = (int)blocks; t.ny = (int)ny;
-        t.sched = sched;
-        if ((rc = c->d_mimo_tail.grow(8 * (size_t)(t.rows * blocks * ny), s, "mimo schedule tail"))) return rc;
-        tail = t.tail = c->d_mimo_tail;
-        const int lr = mpcq_internal_mimo_sched_tail_launch(&t, s);
-        if (lr) return fail(lr == -1 ? MPCQ_ERR_ARG : MPCQ_ERR_HIP, "mimo schedule tail kernel launch failed");
-    }
-    if (log && log->iters_total) HIPCHK(hipMemsetAsync(log->iters_total, 0, 4 * B, s));
-    if (log && log->unsolved_total) HIPCHK(hipMemsetAsync(log->unsolved_total, 0, 4 * B, s));
-    for (int k = 0; k < steps; k++) {
-        const long long step = first_step + k;
-        MimoRef r;
-        if (!sched) {
-            r.yref = yref;
-        } else if (step + N <= sched_len) {
-            r.ref = sched + step * ny; r.stride = sched_stride; r.horizon = true;
-        } else {
-            r.ref = tail + std::min(step - base, N - 1) * ny;
-            r.stride = sched_stride ? blocks * ny : 0;
-            r.horizon = true;
-        }
-        if ((rc = polish ? mimo_step_polish_enqueue(c, X, U, r, s) : mimo_step_enqueue(c, X, U, r, s))) return rc;
-        if ((rc = mimo_plant_enqueue(c, X, U, seed, first_qp, step, noise_std, log, s))) return rc;
-    }
-    return MPCQ_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int mpcq_mimo_set_plant_device(mpcq_ctx *c, const double *Ad, const double *Bd, void *stream)
-{
-    const char *fn = "mpcq_mimo_set_plant_device";
-    int rc = check_ctx(c, kNone);
-    if (rc) return rc;
-    if (c->mode != mpcq_ctx::Mode::Mimo) return fail(MPCQ_ERR_ORDER, "mpcq_mimo_setup_plants_device has not succeeded");
-    if (!Ad || !Bd) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null Ad/Bd");
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = refuse_capture(fn, s))) return rc;
-    const size_t B = c->dims.batch, nx = c->mimo_nx, nu = c->mimo_nu;
-    // (both buffers are released whenever a MIMO setup changes n_x or n_u, so an allocated one has this size)
-    if ((rc = c->d_mimo_Ad.alloc(8 * B * nx * nx, "mimo simulated plant")) ||
-        (rc = c->d_mimo_Bd.alloc(8 * B * nx * nu, "mimo simulated plant")))
-        return rc;
-    HIPCHK(hipMemcpyAsync(c->d_mimo_Ad, Ad, 8 * B * nx * nx, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_mimo_Bd, Bd, 8 * B * nx * nu, hipMemcpyDeviceToDevice, s));
-    c->mimo_plant = true;
-    return MPCQ_OK;
-}
-
-int mpcq_mimo_simulate_device(mpcq_ctx *c, double *X, const double *U, unsigned long long seed, long long first_qp,
-                              long long step, double noise_std, void *stream)
-{
-    const char *fn = "mpcq_mimo_simulate_device";
-    int rc = mimo_plant_check(c, fn);
-    if (rc) return rc;
-    if (!X || !U) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null X/U");
-    if (step < 0) return fail(MPCQ_ERR_ARG, std::string(fn) + ": step >= 0");
-    return mimo_plant_enqueue(c, X, U, seed, first_qp, step, noise_std, nullptr, (hipStream_t)stream);
-}
-
-int mpcq_mimo_run_device(mpcq_ctx *c, double *X, double *U, const double *yref, int steps, unsigned long long seed,
-                         long long first_qp, long long first_step, double noise_std, int polish,
-                         const mpcq_mimo_log *log, void *stream)
-{
-    hipStream_t s = (hipStream_t)stream;
-    int rc = mimo_run_check(c, "mpcq_mimo_run_device", X, U, steps, first_step, polish, log, s);
-    if (rc) return rc;
-    return mimo_run_enqueue(c, X, U, yref, nullptr, 0, 0, steps, seed, first_qp, first_step, noise_std, polish, log, s);
-}
-
-int mpcq_mimo_run_ref_device(mpcq_ctx *c, double *X, double *U, const double *sched, int sched_len,
-                             long long sched_stride, int steps, unsigned long long seed, long long first_qp,
-                             long long first_step, double noise_std, int polish, const mpcq_mimo_log *log, void *stream)
-{
-    const char *fn = "mpcq_mimo_run_ref_device";
-    hipStream_t s = (hipStream_t)stream;
-    int rc = mimo_run_check(c, fn, X, U, steps, first_step, polish, log, s);
-    if (rc) return rc;
-    if (!sched || sched_len < 1) return fail(MPCQ_ERR_ARG, std::string(fn) + ": null schedule or sched_len < 1");
-    if (sched_stride != 0 && sched_stride < (long long)sched_len * c->mimo_ny)
-        return fail(MPCQ_ERR_ARG, std::string(fn) + ": sched_stride is 0 (one schedule for the batch) or >= sched_len*n_y");
-    return mimo_run_enqueue(c, X, U, nullptr, sched, sched_len, sched_stride, steps, seed, first_qp, first_step,
-                            noise_std, polish, log, s);
 }
 
 }  // extern "C"

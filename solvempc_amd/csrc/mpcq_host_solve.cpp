@@ -422,6 +422,18 @@ int dump_tile_stamps(const char *path, const long long *d_stamps, size_t phases,
     return 0;
 }
 
+// `count` stamps of a plant or MIMO kernel's debug build, raw (tools/*stamps*.py read them): MPCQ_OK or MPCQ_ERR_HIP
+int dump_stamps(const char *path, const long long *d_stamps, size_t count, hipStream_t s)
+{
+    std::vector<long long> h(count);
+    HIPCHK(hipMemcpyAsync(h.data(), d_stamps, 8 * count, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (FILE *f = std::fopen(path, "wb")) {
+        std::fwrite(h.data(), 8, count, f);
+        std::fclose(f);
+    }
+    return MPCQ_OK;
+}
 
 // ---- settings.verbose (osqp-eigen setVerbosity, ModelPredictiveControlAPI.cpp:51, solver.cpp:21-25):
 // OSQP v0.6's setup header, its iteration summary line and its status footer, for QP 0 of the context

@@ -16,6 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace mpcq {
 
 // OSQP v0.6 constants (constants.h)
@@ -391,6 +393,29 @@ struct MimoLayout {
         return L;
     }
 };
+
+// The MIMO shape domain: what mpcq_mimo_setup_plants_device accepts and every MIMO launcher serves.
+inline bool mimo_shape_ok(int N, int nx, int nu, int ny)
+{
+    return (nu == 1 || nu == 2 || nu == 4) && nx >= 1 && nx <= 12 && ny >= 1 && ny <= 12 && N >= 1 && N <= 32 &&
+           N * nu <= 128;
+}
+
+// f(std::integral_constant<int, n_u>) for the run-time n_u of a shape mimo_shape_ok accepts
+template <typename F>
+inline auto mimo_with_nu(int nu, F &&f)
+{
+    if (nu == 1) return f(std::integral_constant<int, 1>{});
+    if (nu == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 4>{});
+}
+
+// The active set's rule of a MIMO step's row, polish's on the scaled iterate (l = -DBL_MAX: upper-active rows only):
+// u the row's unscaled upper bound, E its scaling, (z, y) the step's final scaled iterate.
+__host__ __device__ __forceinline__ bool mimo_upper_active(double u, double E, double z, double y)
+{
+    return u * E - z < y;
+}
 
 struct MimoSetupArgs {
     int n_plants, N, nx, nu, ny, s_rows, scaling;

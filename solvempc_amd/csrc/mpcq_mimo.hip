@@ -587,8 +587,7 @@ extern "C" int mpcq_internal_mimo_setup_launch(const mpcq::MimoSetupArgs *a, hip
 {
     const mpcq::MimoSetupShape S = mpcq::MimoSetupShape::make(a->N, a->nx, a->nu, a->ny);
     const size_t lds = 8 * S.total;
-    if (a->nx > 12 || a->nu > 4 || a->ny > 12 || a->N * a->nu > mpcq::kMimoN || a->N > 32 || lds > 160 * 1024)
-        return -1;
+    if (!mpcq::mimo_shape_ok(a->N, a->nx, a->nu, a->ny) || lds > 160 * 1024) return -1;
     if (lds > 64 * 1024 &&
         hipFuncSetAttribute((const void *)mpcq::mimo_setup_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
             hipSuccess)
@@ -599,22 +598,15 @@ extern "C" int mpcq_internal_mimo_setup_launch(const mpcq::MimoSetupArgs *a, hip
 
 extern "C" int mpcq_internal_mimo_solve_launch(const mpcq::MimoArgs *a, hipStream_t s)
 {
-    if (a->nx > 12 || a->ny > 12 || a->N * a->nu > mpcq::kMimoN || a->N > 32) return -1;
+    if (!mpcq::mimo_shape_ok(a->N, a->nx, a->nu, a->ny)) return -1;
     const dim3 grid(a->batch), block(mpcq::kMimoThreads);
-#define MPCQ_MIMO_LAUNCH(U)                                                                  \
-    do {                                                                                     \
-        if (a->diag_k0)                                                                      \
-            hipLaunchKernelGGL((mpcq::mimo_solve_kernel<U, true>), grid, block, 0, s, *a);   \
-        else                                                                                 \
-            hipLaunchKernelGGL((mpcq::mimo_solve_kernel<U, false>), grid, block, 0, s, *a);  \
-    } while (0)
-    switch (a->nu) {
-    case 1: MPCQ_MIMO_LAUNCH(1); break;
-    case 2: MPCQ_MIMO_LAUNCH(2); break;
-    case 4: MPCQ_MIMO_LAUNCH(4); break;
-    default: return -1;
-    }
-#undef MPCQ_MIMO_LAUNCH
+    mpcq::mimo_with_nu(a->nu, [&](auto nu) {
+        constexpr int U = decltype(nu)::value;
+        if (a->diag_k0)
+            hipLaunchKernelGGL((mpcq::mimo_solve_kernel<U, true>), grid, block, 0, s, *a);
+        else
+            hipLaunchKernelGGL((mpcq::mimo_solve_kernel<U, false>), grid, block, 0, s, *a);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -622,24 +614,17 @@ extern "C" int mpcq_internal_mimo_solve_launch(const mpcq::MimoArgs *a, hipStrea
 extern "C" int mpcq_internal_mimo_solve_ref_launch(const mpcq::MimoArgs *a, const double *ref, long long ref_stride,
                                                    hipStream_t s)
 {
-    if (a->nx > 12 || a->ny > 12 || a->N * a->nu > mpcq::kMimoN || a->N > 32) return -1;
+    if (!mpcq::mimo_shape_ok(a->N, a->nx, a->nu, a->ny)) return -1;
     if (!ref || (ref_stride != 0 && ref_stride < (long long)a->N * a->ny)) return -1;
     const dim3 grid(a->batch), block(mpcq::kMimoThreads);
     const mpcq::MimoRefArgs r{*a, ref, ref_stride};
     const size_t lds = 8 * (size_t)a->N * a->nu * a->ny;  // the plant's Frs, staged (<= 12 KiB; 20.3 KiB static)
-#define MPCQ_MIMO_LAUNCH(U)                                                                     \
-    do {                                                                                        \
-        if (a->diag_k0)                                                                         \
-            hipLaunchKernelGGL((mpcq::mimo_solve_ref_kernel<U, true>), grid, block, lds, s, r);   \
-        else                                                                                    \
-            hipLaunchKernelGGL((mpcq::mimo_solve_ref_kernel<U, false>), grid, block, lds, s, r);  \
-    } while (0)
-    switch (a->nu) {
-    case 1: MPCQ_MIMO_LAUNCH(1); break;
-    case 2: MPCQ_MIMO_LAUNCH(2); break;
-    case 4: MPCQ_MIMO_LAUNCH(4); break;
-    default: return -1;
-    }
-#undef MPCQ_MIMO_LAUNCH
+    mpcq::mimo_with_nu(a->nu, [&](auto nu) {
+        constexpr int U = decltype(nu)::value;
+        if (a->diag_k0)
+            hipLaunchKernelGGL((mpcq::mimo_solve_ref_kernel<U, true>), grid, block, lds, s, r);
+        else
+            hipLaunchKernelGGL((mpcq::mimo_solve_ref_kernel<U, false>), grid, block, lds, s, r);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

@@ -17,8 +17,8 @@
 //                 barrier per step; gAd += r_(k-1)' rho_k and gBd += r_(k-1)' GCAB_(k-1) ride along in registers
 // Every output element is owned by one thread that sums in a fixed index order, and the scans are mpcq_lane.h's on
 // one wavefront: no atomics, two calls give identical bits.  Everything is computed whichever outputs are asked for;
-// a null pointer only skips the store.  The active set of y_a is polish's rule restated on the step's scaled iterate
-// (mimo_sens_kernel's expression, operand for operand).  Nothing of the context is written.
+// a null pointer only skips the store.  The active set of y_a is mimo_sens_kernel's (mimo_upper_active on the step's
+// scaled iterate).  Nothing of the context is written.
 #include "mpcq_internal.h"
 #include "mpcq_lane.h"
 
@@ -123,9 +123,8 @@ __global__ __launch_bounds__(kPvThreads) void mimo_plant_vjp_kernel(MimoPlantVjp
         for (int e = t; e < n; e += kPvThreads) {
             const double E = A.ops[P * A.ops_stride + offE + e];
             const size_t it = P * m + e, ib = it + n;
-            // polish's rule on the scaled iterate, as mimo_sens_kernel states it (l = -DBL_MAX: upper-active only)
-            const double uht = A.u[it] * E, uhb = A.u[ib] * E;
-            const bool upt = uht - A.zs[it] < A.ys[it], upb = uhb - A.zs[ib] < A.ys[ib];
+            const bool upt = mimo_upper_active(A.u[it], E, A.zs[it], A.ys[it]);
+            const bool upb = mimo_upper_active(A.u[ib], E, A.zs[ib], A.ys[ib]);
             const double wt = A.gu[it], wb = A.gu[ib];
             a[e] = A.gq[P * n + e];
             b[e] = A.x[P * n + e];
@@ -329,16 +328,11 @@ extern "C" size_t mpcq_internal_mimo_plant_vjp_lds(int N, int nx, int nu, int ny
 extern "C" int mpcq_internal_mimo_plant_vjp_launch(const mpcq::MimoPlantVjpArgs *a, int cus, hipStream_t s, hipError_t *err)
 {
     *err = hipSuccess;
-    if (a->nx <= 0 || a->nx > 12 || a->ny <= 0 || a->ny > 12 || a->N <= 0 || a->N > 32 || a->N * a->nu > 128) return -1;
+    if (!mpcq::mimo_shape_ok(a->N, a->nx, a->nu, a->ny)) return -1;
     if (a->batch <= 0) return 0;
-    void (*kernel)(mpcq::MimoPlantVjpArgs) = nullptr;
-    switch (a->nu) {
-    case 1: kernel = mpcq::mimo_plant_vjp_kernel<1>; break;
-    case 2: kernel = mpcq::mimo_plant_vjp_kernel<2>; break;
-    case 4: kernel = mpcq::mimo_plant_vjp_kernel<4>; break;
-    default: return -1;
-    }
-    // (no static LDS: the carve-up is the call's own N, nx, nu, ny, so a CU holds as many plants as they allow)
-    return mpcq::launch_per_qp(kernel, *a, a->batch, mpcq::kPvThreads, mpcq_internal_mimo_plant_vjp_lds(a->N, a->nx, a->nu, a->ny),
-                               0, cus, s, err);
+    return mpcq::mimo_with_nu(a->nu, [&](auto nu) {
+        // (no static LDS: the carve-up is the call's own N, nx, nu, ny, so a CU holds as many plants as they allow)
+        return mpcq::launch_per_qp(mpcq::mimo_plant_vjp_kernel<decltype(nu)::value>, *a, a->batch, mpcq::kPvThreads,
+                                   mpcq_internal_mimo_plant_vjp_lds(a->N, a->nx, a->nu, a->ny), 0, cus, s, err);
+    });
 }

@@ -24,39 +24,20 @@
 
 namespace mpcq {
 
-// LDS carve-up (doubles) of polish_mimo_kernel for n variables
+// LDS carve-up (doubles) of polish_mimo_kernel for n variables: the reduced KKT system's (b1: -q^; sx: the ADMM x^,
+// then the polished x^; sn: y_a; r1 also: the top half of A^ x^), then the kernel's own
 struct MimoPolishShape {
-    int n, n8, ntri, rows, region;
-    int X, R, sD, sE, b1, sx, sn, r1, r2, ta, tb, tc, wv, pre, dx, dn, bu, ym, pp, sg, ae, posm, act, total;
+    WgKktShape k;
+    int dx, dn, bu, ym, total;
     __host__ __device__ static MimoPolishShape make(int n)
     {
         MimoPolishShape s{};
-        const WgTriShape w = WgTriShape::make(n);
-        s.n = n; s.n8 = w.n8; s.ntri = w.ntri; s.rows = w.rows; s.region = w.region;
-        int o = 0;
-        s.X = o; o += s.ntri;          // H, its factor L, then X = L^-1 (packed lower)
-        s.R = o; o += s.region;        // chunk buffers (prefix sums, V rows), then S, its factor, its inverse
-        s.sD = o; o += n;
-        s.sE = o; o += n;
-        s.b1 = o; o += n;              // -q^
-        s.sx = o; o += n;              // the ADMM x^, then the polished x^
-        s.sn = o; o += s.n8;           // y_a
-        s.r1 = o; o += n;              // residual, variables; the top half of A^ x^
-        s.r2 = o; o += s.n8;           // residual, reduced rows
-        s.ta = o; o += n;              // scratch n-vectors of the solves
-        s.tb = o; o += n;
-        s.tc = o; o += n;
-        s.wv = o; o += s.n8;           // scratch reduced-row vector
-        s.pre = o; o += n;             // prefix / suffix sums of the structured products
+        s.k = WgKktShape::make(n);
+        int o = s.k.total;
         s.dx = o; o += n;              // a refinement step's update; P^ x^ + q^ + A^' y^
-        s.dn = o; o += s.n8;
-        s.bu = o; o += s.n8;           // u^ of the reduced rows
+        s.dn = o; o += s.k.n8;
+        s.bu = o; o += s.k.n8;         // u^ of the reduced rows
         s.ym = o; o += 2 * n;          // y^ of all 2n rows
-        s.pp = o; o += 2 * 128;        // the two halves of P^ x
-        s.sg = o; o += s.n8;           // sign_a E_a of reduced row a
-        s.ae = o; o += (s.n8 + 1) / 2; // (ints) element (k, r) of reduced row a
-        s.posm = o; o += n;            // (ints, 2n) reduced row of QP row i, -1: inactive
-        s.act = o; o += n;             // (ints, 2n) QP row of reduced row a
         s.total = o;
         return s;
     }
@@ -72,13 +53,11 @@ __global__ __launch_bounds__(kWgThreads) void polish_mimo_kernel(MimoPolishArgs 
     const int N = a.N, n = N * NU, m = 2 * n;
     const MimoLayout L = MimoLayout::make(N, a.nx, NU, a.ny);
     const MimoPolishShape S = MimoPolishShape::make(n);
-    double *const X = lds + S.X, *const R = lds + S.R;
-    double *const sD = lds + S.sD, *const sE = lds + S.sE, *const b1 = lds + S.b1, *const sx = lds + S.sx;
-    double *const sn = lds + S.sn, *const r1 = lds + S.r1, *const r2 = lds + S.r2, *const ta = lds + S.ta;
-    double *const tb = lds + S.tb, *const tc = lds + S.tc, *const wvv = lds + S.wv, *const pre = lds + S.pre;
+    WgKkt<NU> K(lds, S.k, s_K0, s_piv, N, t);
+    double *const sD = K.sD, *const b1 = K.b1, *const sx = K.sx, *const sn = K.sn, *const r1 = K.r1;
+    double *const ta = K.ta, *const tc = K.tc, *const pp = K.pp;
     double *const dx = lds + S.dx, *const dn = lds + S.dn, *const bu = lds + S.bu, *const ym = lds + S.ym;
-    double *const pp = lds + S.pp, *const sg = lds + S.sg;
-    int *const ae = (int *)(lds + S.ae), *const posm = (int *)(lds + S.posm), *const act = (int *)(lds + S.act);
+    const int *const posm = K.posm;
     const double nanv = __builtin_nan("");
 
     for (int b = blockIdx.x; b < a.batch; b += gridDim.x) {
@@ -96,31 +75,24 @@ __global__ __launch_bounds__(kWgThreads) void polish_mimo_kernel(MimoPolishArgs 
         const double c = ops[L.cs], cinv = ops[L.cs + 1];
         // ---- P^ + delta I (lower triangle, packed), D, E, K0, -q^ and the step's iterate
         const double *Ph = ops + L.Ph;
-        for (int e = t; e < n * L.ldp; e += kWgThreads) {
-            const int i = e / L.ldp, k = e - i * L.ldp;
-            if (k <= i) X[tri(i) + k] = k == i ? Ph[e] + a.delta : Ph[e];
-        }
+        K.load(ops, L, a.delta);
         if (t < n) {
-            const double Dt = ops[L.D + t];
-            sD[t] = Dt;
-            sE[t] = ops[L.E + t];
-            b1[t] = -((a.q[(size_t)b * n + t] * Dt) * c);
+            b1[t] = -((a.q[(size_t)b * n + t] * sD[t]) * c);
             sx[t] = a.xs[(size_t)b * n + t];
         }
-        if (t < 16) s_K0[t] = ((t >> 2) < NU && (t & 3) < NU) ? ops[L.K0 + (t >> 2) * NU + (t & 3)] : 0.0;
         // ---- 1. the active set (l = -DBL_MAX: no lower-active row); row t's u^, z^, y^ stay in thread t
         double Er = 1.0, uh = 0.0, zh = 0.0, yh = 0.0;
         bool upp = false;
         if (t < m) {
             Er = ops[L.E + (t < n ? t : t - n)];
-            uh = a.u[(size_t)b * m + t] * Er;
+            const double ut = a.u[(size_t)b * m + t];
+            uh = ut * Er;
             zh = a.zs[(size_t)b * m + t];
             yh = a.ys[(size_t)b * m + t];
-            upp = uh - zh < yh;
+            upp = mimo_upper_active(ut, Er, zh, yh);
             ym[t] = yh;
         }
-        const int mr = wg_reduced_rows(upp, m, t, s_cnt, posm, act);
-        const WgKkt<NU> K{N, n, mr, t, X, R, sD, sE, sg, s_K0, ae, posm, pre, ta, tb, tc, wvv};
+        const int mr = K.mr = wg_reduced_rows(upp, m, t, s_cnt, K.posm, K.act);
 
         // row t of A^ x for the x in xv (r1: its top half)
         auto row_ax = [&](const double *xv) {
@@ -158,35 +130,15 @@ __global__ __launch_bounds__(kWgThreads) void polish_mimo_kernel(MimoPolishArgs 
         // ---- 2. the factors
         bool ok = mr <= n;  // (more than n reduced rows: unsuccessful, everything kept)
         if (ok) {
-            if (t < mr) {
-                const int row = act[t], e = row < n ? row : row - n;
-                ae[t] = e;
-                sg[t] = row < n ? sE[e] : -sE[e];
-            }
             if (upp) bu[posm[t]] = uh;
-            ok = wg_cholesky(X, n, t, s_piv);
-            if (ok) wg_tri_invert(X, n, t, ta);
+            ok = K.factor(a.delta);
         }
-        if (ok && mr > 0) ok = K.schur(S.rows, S.n8, a.delta, s_piv);
 
         double pri_p = nanv, dua_p = nanv, zp = 0.0, yp = 0.0;
         if (ok) {
             // ---- 3. the regularised solve, refined against the unregularised matrix
             K.solve(b1, bu, sx, sn);
-            for (int it = 0; it < a.refine; it++) {  // s += K_reg^-1 (b - K s), K without delta
-                wg_sym_mv_halves(Ph, L.ldp, n, sx, pp, t);
-                __syncthreads();
-                if (t < n) tc[t] = b1[t] - (pp[t] + pp[128 + t]);
-                __syncthreads();
-                K.apply_At(sn, tc, ta, r1);
-                K.apply_A(sx, bu, wvv);
-                if (t < mr) r2[t] = -wvv[t];  // (u^_a - A_a x^)
-                __syncthreads();
-                K.solve(r1, r2, dx, dn);
-                if (t < n) sx[t] += dx[t];
-                if (t < mr) sn[t] += dn[t];
-                __syncthreads();
-            }
+            K.refine(Ph, L.ldp, bu, a.refine, dx, dn);
             // ---- 4. the polished point
             const double ax = row_ax(sx);
             if (t < m) {
@@ -233,16 +185,11 @@ extern "C" size_t mpcq_internal_mimo_polish_lds(int n) { return 8 * (size_t)mpcq
 extern "C" int mpcq_internal_mimo_polish_launch(const mpcq::MimoPolishArgs *a, int cus, hipStream_t s, hipError_t *err)
 {
     *err = hipSuccess;
-    const int n = a->N * a->nu;
-    if (a->nx <= 0 || a->nx > 12 || a->ny <= 0 || a->ny > 12 || a->N <= 0 || a->N > 32 || n > 128) return -1;
+    if (!mpcq::mimo_shape_ok(a->N, a->nx, a->nu, a->ny)) return -1;
     if (a->batch <= 0) return 0;
-    void (*kernel)(mpcq::MimoPolishArgs) = nullptr;
-    switch (a->nu) {
-    case 1: kernel = mpcq::polish_mimo_kernel<1>; break;
-    case 2: kernel = mpcq::polish_mimo_kernel<2>; break;
-    case 4: kernel = mpcq::polish_mimo_kernel<4>; break;
-    default: return -1;
-    }
-    // (256: the kernel's few static words)
-    return mpcq::launch_per_qp(kernel, *a, a->batch, mpcq::kWgThreads, mpcq_internal_mimo_polish_lds(n), 256, cus, s, err);
+    return mpcq::mimo_with_nu(a->nu, [&](auto nu) {
+        // (256: the kernel's few static words)
+        return mpcq::launch_per_qp(mpcq::polish_mimo_kernel<decltype(nu)::value>, *a, a->batch, mpcq::kWgThreads,
+                                   mpcq_internal_mimo_polish_lds(a->N * a->nu), 256, cus, s, err);
+    });
 }

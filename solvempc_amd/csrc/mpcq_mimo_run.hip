@@ -1,6 +1,6 @@
 // solvempc_amd/csrc/mpcq_mimo_run.hip — what runs between the control steps of a closed-loop MIMO run
 // (mpcq_mimo_simulate_device, mpcq_mimo_run_device, mpcq_mimo_run_ref_device).  The control step
-// itself is mpcq_mimo.hip's kernels, launched once per step by the host (mpcq_host_plants.cpp), unchanged.
+// itself is mpcq_mimo.hip's kernels, launched once per step by the host (mpcq_host_mimo.cpp), unchanged.
 //   mimo_plant_kernel       the plant update, its noise, the record row and the two totals of one step, one pass
 //   mimo_sched_tail_kernel  the padded tail of a reference schedule, at most once per call
 #include "mpcq_internal.h"

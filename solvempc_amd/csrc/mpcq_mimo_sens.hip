@@ -23,37 +23,17 @@ namespace mpcq {
 
 constexpr int kMsThreads = kWgThreads;
 
-// LDS carve-up (doubles) of mimo_sens_kernel for n variables
+// LDS carve-up (doubles) of mimo_sens_kernel for n variables: the reduced KKT system's, then the kernel's own
 struct MimoSensShape {
-    int n, n8, ntri, rows, region;
-    int X, R, sD, sE, b1, sx, sn, r1, r2, ta, tb, tc, wv, pre, gq, gu, pp, sg, ae, posm, act, total;
+    WgKktShape k;
+    int gq, gu, total;
     __host__ __device__ static MimoSensShape make(int n)
     {
         MimoSensShape s{};
-        const WgTriShape w = WgTriShape::make(n);
-        s.n = n; s.n8 = w.n8; s.ntri = w.ntri; s.rows = w.rows; s.region = w.region;
-        int o = 0;
-        s.X = o; o += s.ntri;          // H, its factor L, then X = L^-1 (packed lower)
-        s.R = o; o += s.region;        // chunk buffers (prefix sums, V rows), then S, its factor, its inverse
-        s.sD = o; o += n;
-        s.sE = o; o += n;
-        s.b1 = o; o += n;              // the scaled right-hand side
-        s.sx = o; o += n;              // v^
-        s.sn = o; o += s.n8;           // w^
-        s.r1 = o; o += n;              // residual / update, variables
-        s.r2 = o; o += s.n8;           // residual / update, reduced rows
-        s.ta = o; o += n;              // scratch n-vectors of the solves
-        s.tb = o; o += n;
-        s.tc = o; o += n;
-        s.wv = o; o += s.n8;           // scratch reduced-row vector
-        s.pre = o; o += n;             // prefix / suffix sums of the structured products
+        s.k = WgKktShape::make(n);
+        int o = s.k.total;
         s.gq = o; o += n;              // this right-hand side's gq, gu (the chain rule reads them)
         s.gu = o; o += 2 * n;
-        s.pp = o; o += 2 * 128;        // the two halves of P^ x
-        s.sg = o; o += s.n8;           // sign_a E_a of reduced row a
-        s.ae = o; o += (s.n8 + 1) / 2; // (ints) element (k, r) of reduced row a
-        s.posm = o; o += n;            // (ints, 2n) reduced row of QP row i, -1: inactive
-        s.act = o; o += n;             // (ints, 2n) QP row of reduced row a
         s.total = o;
         return s;
     }
@@ -69,12 +49,10 @@ __global__ __launch_bounds__(kMsThreads) void mimo_sens_kernel(MimoSensArgs a)
     const int N = a.N, nx = a.nx, ny = a.ny, n = N * NU, m = 2 * n;
     const MimoLayout L = MimoLayout::make(N, nx, NU, ny);
     const MimoSensShape S = MimoSensShape::make(n);
-    double *const X = lds + S.X, *const R = lds + S.R;
-    double *const sD = lds + S.sD, *const sE = lds + S.sE, *const b1 = lds + S.b1, *const sx = lds + S.sx;
-    double *const sn = lds + S.sn, *const r1 = lds + S.r1, *const r2 = lds + S.r2, *const ta = lds + S.ta;
-    double *const tb = lds + S.tb, *const tc = lds + S.tc, *const wvv = lds + S.wv, *const pre = lds + S.pre;
-    double *const gqv = lds + S.gq, *const guv = lds + S.gu, *const pp = lds + S.pp, *const sg = lds + S.sg;
-    int *const ae = (int *)(lds + S.ae), *const posm = (int *)(lds + S.posm), *const act = (int *)(lds + S.act);
+    WgKkt<NU> K(lds, S.k, s_K0, s_piv, N, t);
+    double *const sD = K.sD, *const sE = K.sE, *const b1 = K.b1, *const sx = K.sx, *const sn = K.sn;
+    double *const gqv = lds + S.gq, *const guv = lds + S.gu;
+    const int *const posm = K.posm;
     const int per = nx + NU + ny;                 // chain-rule outputs of one right-hand side
 
     for (int b = blockIdx.x; b < a.batch; b += gridDim.x) {
@@ -84,40 +62,18 @@ __global__ __launch_bounds__(kMsThreads) void mimo_sens_kernel(MimoSensArgs a)
         int mr = 0;
         if (ok) {
             // ---- 1. P^ + delta I (lower triangle, packed), D, E, K0
-            const double *Ph = ops + L.Ph;
-            for (int e = t; e < n * L.ldp; e += kMsThreads) {
-                const int i = e / L.ldp, k = e - i * L.ldp;
-                if (k <= i) X[tri(i) + k] = k == i ? Ph[e] + a.delta : Ph[e];
-            }
-            for (int e = t; e < n; e += kMsThreads) {
-                sD[e] = ops[L.D + e];
-                sE[e] = ops[L.E + e];
-            }
-            if (t < 16) s_K0[t] = ((t >> 2) < NU && (t & 3) < NU) ? ops[L.K0 + (t >> 2) * NU + (t & 3)] : 0.0;
+            K.load(ops, L, a.delta);
             // ---- 2. the active set by polish's rule on the scaled iterate (l = -DBL_MAX: no lower-active row)
             bool upp = false;
-            if (t < m) {
-                const int e = t < n ? t : t - n;
-                const double uh = a.u[(size_t)b * m + t] * ops[L.E + e];
-                const double zh = a.zs[(size_t)b * m + t], yh = a.ys[(size_t)b * m + t];
-                upp = uh - zh < yh;
-            }
-            mr = wg_reduced_rows(upp, m, t, s_cnt, posm, act);
+            if (t < m)
+                upp = mimo_upper_active(a.u[(size_t)b * m + t], ops[L.E + (t < n ? t : t - n)], a.zs[(size_t)b * m + t],
+                                        a.ys[(size_t)b * m + t]);
+            mr = wg_reduced_rows(upp, m, t, s_cnt, K.posm, K.act);
             if (mr > n) ok = false;  // a degenerate bound pair (rows j and n + j both active): no sensitivity
         }
-        const WgKkt<NU> K{N, n, mr, t, X, R, sD, sE, sg, s_K0, ae, posm, pre, ta, tb, tc, wvv};
-        if (ok) {
-            if (t < mr) {
-                const int row = act[t], e = row < n ? row : row - n;
-                ae[t] = e;
-                sg[t] = row < n ? sE[e] : -sE[e];
-            }
-            // ---- 3. H = L L', X = L^-1
-            ok = wg_cholesky(X, n, t, s_piv);
-            if (ok) wg_tri_invert(X, n, t, ta);
-        }
-        // ---- 4. S = delta I + V'V, V = X A_a' formed kWgChunk rows at a time
-        if (ok && mr > 0) ok = K.schur(S.rows, S.n8, a.delta, s_piv);
+        K.mr = mr;
+        // ---- 3. H = L L', X = L^-1;  4. S = delta I + V'V, V = X A_a' formed kWgChunk rows at a time
+        if (ok) ok = K.factor(a.delta);
 
         for (int r = 0; r < a.n_rhs; r++) {
             const size_t br = (size_t)b * a.n_rhs + r;
@@ -129,20 +85,7 @@ __global__ __launch_bounds__(kMsThreads) void mimo_sens_kernel(MimoSensArgs a)
                 }
                 __syncthreads();
                 K.solve(b1, nullptr, sx, sn);
-                for (int it = 0; it < a.refine; it++) {  // s += K_reg^-1 (b - K s), K without delta
-                    wg_sym_mv_halves(ops + L.Ph, L.ldp, n, sx, pp, t);  // P^ v^
-                    __syncthreads();
-                    if (t < n) tc[t] = b1[t] - (pp[t] + pp[128 + t]);
-                    __syncthreads();
-                    K.apply_At(sn, tc, ta, r1);
-                    K.apply_A(sx, nullptr, wvv);
-                    if (t < mr) r2[t] = -wvv[t];  // (the unregularised matrix: 0 - A_a v^)
-                    __syncthreads();
-                    K.solve(r1, r2, gqv, guv);  // (gqv, guv: free until the results below)
-                    if (t < n) sx[t] += gqv[t];
-                    if (t < mr) sn[t] += guv[t];
-                    __syncthreads();
-                }
+                K.refine(ops + L.Ph, L.ldp, nullptr, a.refine, gqv, guv);  // (gqv, guv: free until the results below)
                 if (t < n) gqv[t] = -(sx[t] * sD[t]);
                 if (t < m) {
                     const int e = t < n ? t : t - n, p = posm[t];
@@ -215,17 +158,11 @@ extern "C" size_t mpcq_internal_mimo_sens_lds(int n) { return 8 * (size_t)mpcq::
 extern "C" int mpcq_internal_mimo_sens_launch(const mpcq::MimoSensArgs *a, int cus, hipStream_t s, hipError_t *err)
 {
     *err = hipSuccess;
-    const int n = a->N * a->nu;
-    if (a->nx <= 0 || a->nx > 12 || a->ny <= 0 || a->ny > 12 || a->N <= 0 || a->N > 32 || n > 128) return -1;
-    if (a->n_rhs < 1 || a->n_rhs > 4) return -1;
+    if (!mpcq::mimo_shape_ok(a->N, a->nx, a->nu, a->ny) || a->n_rhs < 1 || a->n_rhs > 4) return -1;
     if (a->batch <= 0) return 0;
-    void (*kernel)(mpcq::MimoSensArgs) = nullptr;
-    switch (a->nu) {
-    case 1: kernel = mpcq::mimo_sens_kernel<1>; break;
-    case 2: kernel = mpcq::mimo_sens_kernel<2>; break;
-    case 4: kernel = mpcq::mimo_sens_kernel<4>; break;
-    default: return -1;
-    }
-    // (256: the kernel's few static words)
-    return mpcq::launch_per_qp(kernel, *a, a->batch, mpcq::kMsThreads, mpcq_internal_mimo_sens_lds(n), 256, cus, s, err);
+    return mpcq::mimo_with_nu(a->nu, [&](auto nu) {
+        // (256: the kernel's few static words)
+        return mpcq::launch_per_qp(mpcq::mimo_sens_kernel<decltype(nu)::value>, *a, a->batch, mpcq::kMsThreads,
+                                   mpcq_internal_mimo_sens_lds(a->N * a->nu), 256, cus, s, err);
+    });
 }

@@ -21,13 +21,15 @@ namespace mpcq {
 constexpr int kWgThreads = 256;
 constexpr int kWgChunk = 32;   // rows of V formed at a time (n = 128: 32 x (128 + 128) doubles fit S's region)
 
-// The two packed triangles of a workgroup for n variables (doubles): H's (ntri) and the region that holds the chunk
-// buffers (`rows` rows of n prefix sums and n8 entries of V) and then S (at most n reduced rows).
-struct WgTriShape {
+// LDS carve-up (doubles) of the reduced KKT system for n variables: what both kernels keep there.  A kernel's own
+// vectors follow from `total` on.  The two packed triangles are H's (ntri) and the region that holds the chunk buffers
+// (`rows` rows of n prefix sums and n8 entries of V) and then S (at most n reduced rows).
+struct WgKktShape {
     int n, n8, ntri, rows, region;
-    __host__ __device__ static WgTriShape make(int n)
+    int X, R, sD, sE, b1, sx, sn, r1, r2, ta, tb, tc, wv, pre, pp, sg, ae, posm, act, total;
+    __host__ __device__ static WgKktShape make(int n)
     {
-        WgTriShape s{};
+        WgKktShape s{};
         s.n = n;
         s.n8 = (n + 7) & ~7;
         s.ntri = n * (n + 1) / 2;
@@ -36,6 +38,27 @@ struct WgTriShape {
         rows = rows < 1 ? 1 : (rows > kWgChunk ? kWgChunk : rows);
         s.rows = rows;
         s.region = s.ntri > rows * per_row ? s.ntri : rows * per_row;
+        int o = 0;
+        s.X = o; o += s.ntri;          // H, its factor L, then X = L^-1 (packed lower)
+        s.R = o; o += s.region;        // chunk buffers (prefix sums, V rows), then S, its factor, its inverse
+        s.sD = o; o += n;
+        s.sE = o; o += n;
+        s.b1 = o; o += n;              // the scaled right-hand side, variables
+        s.sx = o; o += n;              // the solution, variables
+        s.sn = o; o += s.n8;           // the solution, reduced rows
+        s.r1 = o; o += n;              // residual, variables
+        s.r2 = o; o += s.n8;           // residual, reduced rows
+        s.ta = o; o += n;              // scratch n-vectors of the solves
+        s.tb = o; o += n;
+        s.tc = o; o += n;
+        s.wv = o; o += s.n8;           // scratch reduced-row vector
+        s.pre = o; o += n;             // prefix / suffix sums of the structured products
+        s.pp = o; o += 2 * 128;        // the two halves of P^ x
+        s.sg = o; o += s.n8;           // sign_a E_a of reduced row a
+        s.ae = o; o += (s.n8 + 1) / 2; // (ints) element (k, r) of reduced row a
+        s.posm = o; o += n;            // (ints, 2n) reduced row of QP row i, -1: inactive
+        s.act = o; o += n;             // (ints, 2n) QP row of reduced row a
+        s.total = o;
         return s;
     }
 };
@@ -176,23 +199,58 @@ __device__ __forceinline__ void wg_sym_mv_halves(const double *Ph, int ldp, int 
     }
 }
 
-// The reduced KKT system [H, A_a'; A_a, -delta I] of one QP once its pieces are in LDS: the structured products
-// with A_a (mr reduced rows; ae: element (k, r) of a reduced row, sg: its sign times E) and A_a' (posm: the reduced
-// row of a QP row or -1), the Schur complement, and the solve by the two inverted factors X (of H) and R (of S).
-// ta, tb, tc: scratch n-vectors, wv: a scratch reduced-row vector, pre: n prefix / suffix sums; K0: 4 x 4, zero
-// padded.  Every member ends with a barrier.
+// The reduced KKT system [H, A_a'; A_a, -delta I] of one QP in the LDS of WgKktShape: its load from the operator
+// block, its factors, the structured products with A_a (mr reduced rows; ae: element (k, r) of a reduced row, sg: its
+// sign times E) and A_a' (posm: the reduced row of a QP row or -1), the solve by the two inverted factors X (of H)
+// and R (of S), and its refinement.  K0: 4 x 4, zero padded; piv: 2 doubles.  mr is the caller's to set
+// (wg_reduced_rows on posm, act) before factor().  Every member but load() ends with a barrier.
 template <int NU>
 struct WgKkt {
     static constexpr int LNU = NU == 4 ? 2 : (NU == 2 ? 1 : 0);
-    int N, n, mr, t;
-    double *X, *R;
-    const double *sD, *sE, *sg, *K0;
-    const int *ae, *posm;
-    double *pre, *ta, *tb, *tc, *wv;
+    int N, n, n8, rows_cap, t, mr = 0;
+    double *X, *R, *sD, *sE, *b1, *sx, *sn, *r1, *r2, *ta, *tb, *tc, *wv, *pre, *pp, *sg, *K0, *piv;
+    int *ae, *posm, *act;
 
-    // S = delta I + V'V into R (V = X A_a' formed `rows` rows at a time in R's chunk buffers), factored and inverted
-    // in place; mr > 0.  False when a pivot of S is not positive.  piv: 2 doubles.
-    __device__ __forceinline__ bool schur(int rows_cap, int n8, double delta, double *piv) const
+    __device__ __forceinline__ WgKkt(double *lds, const WgKktShape &S, double *K0_, double *piv_, int N_, int t_)
+        : N(N_), n(S.n), n8(S.n8), rows_cap(S.rows), t(t_), X(lds + S.X), R(lds + S.R), sD(lds + S.sD), sE(lds + S.sE),
+          b1(lds + S.b1), sx(lds + S.sx), sn(lds + S.sn), r1(lds + S.r1), r2(lds + S.r2), ta(lds + S.ta), tb(lds + S.tb),
+          tc(lds + S.tc), wv(lds + S.wv), pre(lds + S.pre), pp(lds + S.pp), sg(lds + S.sg), K0(K0_), piv(piv_),
+          ae((int *)(lds + S.ae)), posm((int *)(lds + S.posm)), act((int *)(lds + S.act))
+    {
+    }
+
+    // P^ + delta I (lower triangle, packed) into X, D, E and K0 from a plant's operator block.  No trailing barrier.
+    __device__ __forceinline__ void load(const double *ops, const MimoLayout &L, double delta) const
+    {
+        const double *Ph = ops + L.Ph;
+        for (int e = t; e < n * L.ldp; e += kWgThreads) {
+            const int i = e / L.ldp, k = e - i * L.ldp;
+            if (k <= i) X[tri(i) + k] = k == i ? Ph[e] + delta : Ph[e];
+        }
+        if (t < n) {
+            sD[t] = ops[L.D + t];
+            sE[t] = ops[L.E + t];
+        }
+        if (t < 16) K0[t] = ((t >> 2) < NU && (t & 3) < NU) ? ops[L.K0 + (t >> 2) * NU + (t & 3)] : 0.0;
+    }
+
+    // ae, sg of the mr <= n reduced rows, H = L L' and X = L^-1, then S (mr > 0).  False when a pivot is not positive.
+    __device__ __forceinline__ bool factor(double delta) const
+    {
+        if (t < mr) {
+            const int row = act[t], e = row < n ? row : row - n;
+            ae[t] = e;
+            sg[t] = row < n ? sE[e] : -sE[e];
+        }
+        bool ok = wg_cholesky(X, n, t, piv);
+        if (ok) wg_tri_invert(X, n, t, ta);
+        if (ok && mr > 0) ok = schur(delta);
+        return ok;
+    }
+
+    // S = delta I + V'V into R (V = X A_a' formed `rows_cap` rows at a time in R's chunk buffers), factored and
+    // inverted in place; mr > 0.  False when a pivot of S is not positive.
+    __device__ __forceinline__ bool schur(double delta) const
     {
         double *const preC = R;                  // [rows][n]   prefix sums of the chunk's rows of X D
         double *const Vc = R + rows_cap * n;     // [rows][n8]  the chunk's rows of V
@@ -358,6 +416,27 @@ struct WgKkt {
         apply_At(on, p1, ta, tb);
         tri_mv(X, n, tb, ta, t);
         tri_mv_t(X, n, ta, ox, t);
+    }
+
+    // `iters` steps of s += K_reg^-1 (b - K s) on s = (sx, sn), K without delta: b = (b1, sub), sub null: zero; P^ is
+    // read as symmetric from the operator block (Ph, row stride ldp).  ux, un: the update's buffers, as solve()'s.
+    __device__ __forceinline__ void refine(const double *Ph, int ldp, const double *sub, int iters, double *ux,
+                                           double *un) const
+    {
+        for (int it = 0; it < iters; it++) {
+            wg_sym_mv_halves(Ph, ldp, n, sx, pp, t);
+            __syncthreads();
+            if (t < n) tc[t] = b1[t] - (pp[t] + pp[128 + t]);
+            __syncthreads();
+            apply_At(sn, tc, ta, r1);
+            apply_A(sx, sub, wv);
+            if (t < mr) r2[t] = -wv[t];  // (sub - A_a x^)
+            __syncthreads();
+            solve(r1, r2, ux, un);
+            if (t < n) sx[t] += ux[t];
+            if (t < mr) sn[t] += un[t];
+            __syncthreads();
+        }
     }
 };
 
